@@ -6,15 +6,23 @@ synchronous majority sweeps of R = 4096 bit-packed replicas on a d=4 random
 regular graph with N = 1e6 nodes (configs[1]'s sizes, d=4 as the metric
 names), with the per-replica +1 count fused into the last sweep.  Every step
 starts from the same resident synthetic s0 (one SA-style scoring pass).
-Inputs are resident in HBM before the timed region.
+Inputs are resident in HBM before the timed region.  The roofline of the
+dominant kernel (k_sweep_ell_rp) comes from HIP events around the same steps.
 
 Multi-GPU (torch.distributed.run, one rank per GPU): each rank owns its own
 graph instance and replicas (weak scaling, no data-path collective); the
 timed region is bracketed by barrier + synchronize and the max over ranks is
 reported.
 
-Secondary line items in the same JSON object:
-  * roofline of the dominant kernel (k_sweep_ell_rp) from HIP events,
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps, writes the last step's outputs if --dump-outputs DIR is given, and
+prints the result line: nothing else.  --dump-outputs writes DIR/counts.npy
+(float64: the per-replica +1 counts the step returns) and
+DIR/s_end_sample.npy (float32 +-1 spins, nodes x replicas: the end state the
+step returns at a fixed, seeded sample of nodes); the inputs are seeded, so
+two builds can be compared output for output.
+
+Secondary line items, measured only with --full, in the same JSON object:
   * cpu_baseline: the numpy restatement of the reference's onestep_majority
     (oracle/majority.py, same numpy ops as code/SA_RRG.py:18-20) on the same
     graph, one process per core, bounded sample, rank 0 at N=1 only,
@@ -52,6 +60,14 @@ def parse():
     ap.add_argument("--p", type=int, default=2)
     ap.add_argument("--c", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the fixed-point "
+                         "check and the sa / sa_c1 / sa_consensus / sa_global / er / hpr / bdcm / giant legs "
+                         "(each with its own --no-* switch), the detail file and the `summary`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy: counts "
+                         "(float64, per-replica +1 counts) and s_end_sample (float32 +-1 spins, the end state at "
+                         "a fixed seeded sample of nodes x all replicas)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sa-steps", type=int, default=2000)
@@ -93,9 +109,9 @@ def parse():
     ap.add_argument("--bdcm-iters", type=int, default=100)
     ap.add_argument("--no-bdcm", action="store_true")
     ap.add_argument("--detail-out", default=None,
-                    help="file for the full JSON object (every leg with its notes and per-replica arrays); the "
-                         "printed line keeps each leg's numbers and ends with a compact `summary` (default "
-                         "gpurun_out/bench_detail.json)")
+                    help="with --full: file for the full JSON object (every leg with its notes and per-replica "
+                         "arrays); the printed line keeps each leg's numbers and ends with a compact `summary` "
+                         "(default bench_out/bench_detail.json)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: the ranks join a gloo group, time an empty step and "
                          "rank 0 prints the merged JSON line (tests/test_bench_launch.py)")
@@ -923,6 +939,30 @@ def er_sweep_traffic():
     return {"plain_sweep_bytes": plain, "counting_sweep_bytes": count} if plain and count else None
 
 
+DUMP_NODES = 2048          # nodes of the end state --dump-outputs samples (all replicas of each)
+DUMP_SEED = 20240607
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(path, out, counts, n, W, R, rank):
+    """--dump-outputs: what the last timed step handed its caller -- `counts`
+    (the per-replica +1 counts, exact in float64) and the packed end state
+    `out`, of which a fixed seeded sample of nodes is kept (the whole state is
+    n * R bits; the counts already sum over every node), unpacked on the host
+    to +-1 float32 as (nodes, replicas): bit b of word w is replica 64 w + b,
+    set = +1 (k_pack_rp).  Rank r > 0 writes <name>.rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    m = max(1, min(n, DUMP_NODES, DUMP_MAX_BYTES // (4 * R)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    rows = out.view(n, W)[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    bits = np.unpackbits(np.ascontiguousarray(rows).view(np.uint8).reshape(m, 8 * W), axis=1, bitorder="little")
+    spins = (2.0 * bits[:, :R] - 1.0).astype(np.float32)
+    tag = "" if rank == 0 else f".rank{rank}"
+    np.save(os.path.join(path, f"counts{tag}.npy"), counts.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, f"s_end_sample{tag}.npy"), spins)
+
+
 LEG_KEYS = ("sa", "sa_c1", "sa_consensus", "sa_global", "er", "hpr", "bdcm", "giant")
 # prose and per-replica arrays: kept in the detail file, not on the printed line
 _DROP = {"config", "sample", "host", "note", "loop_note", "device_loop", "done_num_steps", "source",
@@ -998,7 +1038,7 @@ def main():
     adj = mjx.random_regular_graph(d, n, seed=args.seed + 1000 * rank)
 
     cpu = c1_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(adj, T, args.cpu_seconds)
         if not args.no_sa and args.c1_steps > 0:
             c1_cpu = sa_cpu_baseline(c1_graphs(args, 0), 1, 1, list(range(64)), args.c1_cpu_seconds)
@@ -1058,40 +1098,47 @@ def main():
     achieved = bytes_per_sweep / sweep_s / 1e9
     traffic = rocprof_traffic()
 
-    # sanity: the rollout of a constant state is the same constant state
-    chk = torch.full_like(s0, -1)
-    ck = torch.zeros_like(counts)
-    o2 = mjx.rollout(g, chk, T, words=W, counts=ck)
-    assert torch.equal(o2, chk) and bool((ck == n).all()), "fixed-point check failed"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, counts, n, W, R, rank)
+
+    # everything below the headline figure runs with --full only
+    full = args.full
+    if full:
+        # sanity: the rollout of a constant state is the same constant state
+        chk = torch.full_like(s0, -1)
+        ck = torch.zeros_like(counts)
+        o2 = mjx.rollout(g, chk, T, words=W, counts=ck)
+        assert torch.equal(o2, chk) and bool((ck == n).all()), "fixed-point check failed"
+        del chk, o2
 
     sa_res = None
-    if not args.no_sa and args.sa_steps > 0:
+    if full and not args.no_sa and args.sa_steps > 0:
         sa_res = bench_sa(args, rank, world, dist, dev)
     c1 = None
-    if not args.no_sa and args.c1_steps > 0:
+    if full and not args.no_sa and args.c1_steps > 0:
         c1 = bench_sa_c1(args, rank, world, dist, dev, c1_cpu)
     cons = None
-    if not args.no_sa and not args.no_consensus and args.consensus_replicas > 0:
+    if full and not args.no_sa and not args.no_consensus and args.consensus_replicas > 0:
         cons = bench_sa_consensus(args, rank, world, dist, dev)
     sglob = None
-    if not args.no_sa and not args.no_global and args.global_nstat > 0:
+    if full and not args.no_sa and not args.no_global and args.global_nstat > 0:
         sglob = bench_sa_global(args, rank, world, dist, dev)
 
-    del s0, out, tmp, counts, chk, o2
+    del s0, out, tmp, counts
     torch.cuda.empty_cache()
     er = None
-    if not args.no_er and args.er_n > 0:
+    if full and not args.no_er and args.er_n > 0:
         er = bench_er(args, rank, world, dist, dev)
         torch.cuda.empty_cache()
     hpr = None
-    if not args.no_hpr and args.hpr_iters > 0:
+    if full and not args.no_hpr and args.hpr_iters > 0:
         hpr = bench_hpr(args, rank, world, dist, dev)
         torch.cuda.empty_cache()
     bdcm = None
-    if not args.no_bdcm and args.bdcm_iters > 0:
+    if full and not args.no_bdcm and args.bdcm_iters > 0:
         bdcm = bench_bdcm(args, rank, world, dist, dev)
     giant = None
-    if not args.no_giant and args.giant_n > 0:
+    if full and not args.no_giant and args.giant_n > 0:
         giant = bench_giant(args, rank, world, dist, dev)
 
     for leg in (sa_res, c1, cons, sglob, er, hpr, bdcm, giant):
@@ -1129,27 +1176,24 @@ def main():
                 "bytes_per_launch": bytes_per_sweep,
                 "avg_launch_us": sweep_s * 1e6,
             },
-            "cpu_baseline": cpu,
-            "sa": sa_res,
-            "sa_c1": c1,
-            "sa_consensus": cons,
-            "sa_global": sglob,
-            "er": er,
-            "hpr": hpr,
-            "bdcm": bdcm,
-            "giant": giant,
+            "full": full,
         }
-        detail = args.detail_out or os.path.join(ROOT, "gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(line, f, indent=1)
-        except OSError as e:
-            print(f"bench.py: could not write {detail}: {e}", file=sys.stderr, flush=True)
-        out = {k: (compact(v) if k in LEG_KEYS else v) for k, v in line.items()}
-        out["detail_file"] = os.path.relpath(detail, ROOT) if detail.startswith(ROOT) else detail
-        out["summary"] = summary(line)                  # the LAST key: inside any tail of the line
-        print(json.dumps(out, separators=(",", ":")), flush=True)
+        if not full:
+            print(json.dumps(line, separators=(",", ":")), flush=True)
+        else:
+            line.update({"cpu_baseline": cpu, "sa": sa_res, "sa_c1": c1, "sa_consensus": cons, "sa_global": sglob,
+                         "er": er, "hpr": hpr, "bdcm": bdcm, "giant": giant})
+            detail = args.detail_out or os.path.join(ROOT, "bench_out", "bench_detail.json")
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
+                with open(detail, "w") as f:
+                    json.dump(line, f, indent=1)
+            except OSError as e:
+                print(f"bench.py: could not write {detail}: {e}", file=sys.stderr, flush=True)
+            printed = {k: (compact(v) if k in LEG_KEYS else v) for k, v in line.items()}
+            printed["detail_file"] = os.path.relpath(detail, ROOT) if detail.startswith(ROOT) else detail
+            printed["summary"] = summary(line)          # the LAST key: inside any tail of the line
+            print(json.dumps(printed, separators=(",", ":")), flush=True)
     if dist:
         dist.destroy_process_group()
 

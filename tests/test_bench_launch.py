@@ -95,6 +95,52 @@ def test_bench_reads_committed_pmc_traffic():
     assert abs(er["counting_sweep_bytes"] / er["plain_sweep_bytes"] - 1) < 0.05
 
 
+def test_dump_outputs_unpacks_the_sampled_rows(tmp_path):
+    """--dump-outputs: counts as float64, and the packed end state at the
+    seeded node sample as +-1 float32 (nodes, replicas) -- bit b of word w of a
+    node's row is replica 64 w + b, set = +1.  Packed here on the host from
+    known spins; R = 130 leaves 62 unused bits in the last word."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, R = 5000, 130
+    W = (R + 63) // 64
+    rng = np.random.default_rng(3)
+    plus = rng.integers(0, 2, size=(n, R)).astype(np.uint64)              # 1 = spin +1
+    words = np.zeros((n, W), dtype=np.uint64)
+    for r in range(R):
+        words[:, r // 64] |= plus[:, r] << np.uint64(r % 64)
+    words[:, W - 1] |= np.uint64(0xFFFF) << np.uint64(48)                 # junk above replica R-1: never dumped
+    out = torch.from_numpy(words.view(np.int64).reshape(-1))
+    counts = torch.from_numpy(np.concatenate([plus.sum(0), np.zeros(W * 64 - R, np.uint64)]).astype(np.int64))
+    for _ in range(2):                                                    # the sample is the same every time
+        bench.dump_outputs(str(tmp_path), out, counts, n, W, R, 0)
+        c = np.load(tmp_path / "counts.npy")
+        s = np.load(tmp_path / "s_end_sample.npy")
+        assert c.dtype == np.float64 and np.array_equal(c, counts.numpy())
+        idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, size=bench.DUMP_NODES, replace=False))
+        assert s.dtype == np.float32 and s.shape == (bench.DUMP_NODES, R)
+        assert np.array_equal(s, 2.0 * plus[idx].astype(np.float32) - 1.0)
+    assert c.nbytes + s.nbytes <= 64 << 20
+    bench.dump_outputs(str(tmp_path), out, counts, n, W, R, 1)
+    assert np.array_equal(np.load(tmp_path / "s_end_sample.rank1.npy"), s)
+    # the default workload's dump (n = 1e6, R = 4096) stays under 64 MB
+    m = min(1_000_000, bench.DUMP_NODES, bench.DUMP_MAX_BYTES // (4 * 4096))
+    assert m * 4096 * 4 + 4096 * 8 <= 64 << 20
+
+
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_printed_line_is_compact_and_ends_with_the_summary():
     """the driver keeps only the tail of stdout (~8 KB, the
     record's `tail` 2 KB), so the printed line keeps each leg's numbers, moves

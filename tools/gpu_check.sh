@@ -6,6 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out
 mkdir -p $OUT
+ROOT="$(pwd)"
 export PYTHONUNBUFFERED=1
 stop_if_fatal() {  # $1 = status, $2 = step name
   if [ "$1" -ne 0 ] && [ "$1" -ne 1 ]; then
@@ -37,12 +38,12 @@ for s in $STEPS; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       stop_if_fatal $? smoke ;;
     bench)
-      timeout -k 10 400 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
+      timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
       stop_if_fatal $? bench ;;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats \
           -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run --output-format csv -- \
-          python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline ${PROF_ARGS:-${BENCH_ARGS:-}} ) > $OUT/prof.log 2>&1
+          python3 "$ROOT/bench.py" --full --no-cpu-baseline ${PROF_ARGS:-${BENCH_ARGS:-}} ) > $OUT/prof.log 2>&1
       stop_if_fatal $? prof ;;
     pmc)
       R="$GRAFT_REPO_ROOT"
