@@ -335,6 +335,71 @@ int mjx_sa_lds_steps(const int32_t* adj, int64_t n, int d, int p, int c, int64_t
                      mjx_sa_state* st, int64_t nsteps, double par_a, double par_b, double a_cap, double b_cap,
                      int64_t t_cap, void* stream);
 
+/* ---- simulated annealing on irregular graphs (CSR) ----------------------- */
+/* The loop of code/SA_RRG.py:65-85 on a graph given as CSR (row_ptr int64
+ * [n+1], col int32 [nnz]; one graph for all replicas), scored with the
+ * notebook's ER end state (nb:113-123: sign(2S+s), a degree-0 node keeps its
+ * spin).  Replica r replays np.random.seed(seeds[r]) exactly as on regular
+ * graphs; the schedule constants are the caller's (schedule of n = the node
+ * count of the graph as passed).  Row entries count with multiplicity (a
+ * self-loop or a doubled edge contributes as often as it is listed).  On the
+ * CSR of a d-regular neighbour array every call is bit-identical to its
+ * mjx_sa_* counterpart.
+ *
+ * PRECONDITION of the light-cone calls: the adjacency is symmetric as a
+ * multiset of directed entries (v appears in row(u) as often as u in row(v)).
+ * The light cone finds the nodes that read a changed node in that node's own
+ * row.  The full-rollout calls (init, steps) do not need it.
+ * st->rep_graph and (steps) st->philox_key are refused with MJX_EINVAL. */
+int mjx_sa_csr_init(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t R,
+                    const uint32_t* seeds, double a0, double b0, uint64_t* s, uint64_t* tmp1, uint64_t* tmp2,
+                    mjx_sa_state* st, void* stream);
+int mjx_sa_csr_init_mt(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t R,
+                       const uint32_t* mt_in, const int32_t* idx_in, double a0, double b0, uint64_t* s,
+                       uint64_t* tmp1, uint64_t* tmp2, mjx_sa_state* st, void* stream);
+/* Full-rollout step (the exact slow path and in-library cross-check):
+ * proposal, mjx_rollout_csr_rp with the fused +1 count, Metropolis test. */
+int mjx_sa_csr_steps(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t R,
+                     uint64_t* s, uint64_t* tmp1, uint64_t* tmp2, mjx_sa_state* st, int64_t nsteps,
+                     double par_a, double par_b, double a_cap, double b_cap, int64_t t_cap, void* stream);
+/* Ball bound: B_0(v) = 1, B_t(v) = 1 + sum_{k in row(v)} B_{t-1}(k) (walks of
+ * length <= t from v), saturating; bound_out[t] = min(n, max_v B_t(v)), t =
+ * 0..T (HOST array).  cap_t bounds the candidate set and the changed set of
+ * level t of any proposal.  work: mjx_sa_csr_ball_work_bytes(n) bytes of device
+ * scratch.  Setup call: synchronises `stream`.  0 <= T <= 6. */
+int64_t mjx_sa_csr_ball_work_bytes(int64_t n);
+int mjx_sa_csr_ball_bound(const int64_t* row_ptr, const int32_t* col, int64_t n, int T, void* work,
+                          int64_t* bound_out, void* stream);
+/* Light-cone step on CSR.  Per replica T+2 lists (changed nodes of levels
+ * 0..T, candidates); the first lds_entries entries of each list per lane live
+ * in LDS (0 = the library's choice, 32), the rest in the caller's spill area.
+ * caps: HOST int64 [T+1] from mjx_sa_csr_ball_bound (any graph within its caps
+ * is evaluated exactly; a replica whose lists outgrow wrong caps stops with
+ * done = 3, nothing is written out of bounds).
+ * _lds: LDS bytes of a workgroup (-1: T or lds_entries out of range, more than
+ * 150 KiB); _scratch_bytes: bytes of spill area for R replicas (0 when every
+ * list fits LDS; -1 on bad arguments). */
+int64_t mjx_sa_csr_lightcone_lds(int T, int lds_entries);
+int64_t mjx_sa_csr_lightcone_scratch_bytes(int64_t R, int T, const int64_t* caps, int lds_entries);
+/* levels[t-1] = onestep^t(s), t = 1..T = p+c-1 (mjx_rollout_csr_rp) */
+int mjx_sa_csr_lightcone_prepare(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t R,
+                                 const uint64_t* s, uint64_t* const* levels, void* stream);
+/* One persistent launch over nsteps proposals, a wave per word column of 64
+ * replicas (st->opt_split waves per column when set, as mjx_sa_lightcone_steps);
+ * proposals are drawn in the step (no tape: the streams stand exactly where
+ * numpy's would); honours the trace pointers and tr_tie; s and levels are kept
+ * current.  MJX_EINVAL for st->rep_graph, st->philox_key, T < 1, T > 6 or
+ * spill_bytes below _scratch_bytes.  No allocation, no host synchronisation. */
+int mjx_sa_csr_lightcone_steps(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t R,
+                               uint64_t* s, uint64_t* const* levels, mjx_sa_state* st, int64_t nsteps,
+                               double par_a, double par_b, double a_cap, double b_cap, int64_t t_cap,
+                               const int64_t* caps, int lds_entries, void* spill, int64_t spill_bytes,
+                               void* stream);
+/* Diagnostic: out2[0] = proposals evaluated by mjx_sa_csr_lightcone_steps on
+ * the current device since the last reset, out2[1] = those with a list longer
+ * than its LDS part (the spill rate's numerator).  Synchronises the device. */
+int mjx_sa_csr_lightcone_stats(unsigned long long* out2, int reset);
+
 /* ---- history-passing reinforcement on d-regular graphs ------------------ */
 /*
  * Message arrays use the reference's layout (code/HPR_pytorch_RRG.py:277-285, 46-61):

@@ -15,6 +15,7 @@ from .npz import (save_sa_npz, save_hpr_npz, save_bdcm_npz, sa_arrays, hpr_array
                   graphs_from_npz)
 from .dynamics import onestep_majority, s_endstate, m, pack, unpack, rollout, popcount, as_graph
 from .sa import SAReplicas, E_delta, sa_run, schedule_constants
+from .sa_er import SAReplicasER, sa_er_run
 from .hpr import HPRPlan, HPRState, HPr_dp, marginals_comp, new_biases_i, hpr_run
 from .hpr_er import HPRERPlan, HPr_dp_er, marginals_comp_er, hpr_er_plan, hpr_er_run
 from .bdcm import (BDCMPlan, bdcm_er_plan, BDCM_ER, bdcm_leaf_reset, Zij, Zi_ER, phi_BP_GENERAL_ER,
@@ -27,6 +28,7 @@ __all__ = [
     "random_regular_edges", "erdos_renyi", "erdos_renyi_device", "erdos_renyi_edges", "csr_from_edges", "remove_isolated",
     "onestep_majority", "s_endstate", "m", "pack", "unpack", "rollout", "popcount", "as_graph",
     "SAReplicas", "E_delta", "sa_run", "schedule_constants",
+    "SAReplicasER", "sa_er_run",
     "HPRPlan", "HPRState", "HPr_dp", "marginals_comp", "new_biases_i", "hpr_run",
     "HPRERPlan", "HPr_dp_er", "marginals_comp_er", "hpr_er_plan", "hpr_er_run",
     "BDCMPlan", "bdcm_er_plan", "BDCM_ER", "bdcm_converge", "bdcm_leaf_reset", "Zij", "Zi_ER", "phi_BP_GENERAL_ER",

@@ -1,9 +1,13 @@
-"""Script-shaped fronts: ``python -m mjx sa|hpr|bdcm`` run the reference's three
+"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm`` run the reference's three
 experiments with its module constants as flags -- same names, same defaults --
 and write its np.savez keys.
 
   sa    code/SA_RRG.py:44-52 (n, d, p, c, par_a, par_b, N_stat), loop :58-88,
         output :92 ("MCMC_p{p}_d{d}.npz": mag_reached, num_steps, conf, graphs)
+  sa-er the same SA loop on one Erdos-Renyi graph (n, deg = mean degree, p, c,
+        par_a, par_b, N_stat), scored with the notebook's ER end state
+        (nb:113-123); output "SA_ER_p{p}.npz": mag_reached, num_steps, conf,
+        done, near_ties, wall_s, row_ptr, col, n_iso
   hpr   code/HPR_pytorch_RRG.py:224-237 (n, d, p, c, damppar, attr_value,
         lmbd_in, pie, gamma, TT) and :251 (n_rep), output :377
         ("hpr_d{d}_p{p}.npz": mag_reached, conf, num_steps, graphs, time)
@@ -31,6 +35,15 @@ SA_DEFAULTS = {            # code/SA_RRG.py
     "p": 3,                # :46
     "c": 1,                # :47
     "par_a": 1.0005,       # :49
+    "par_b": 1.0005,       # :50
+    "N_stat": 5,           # :52
+}
+SA_ER_DEFAULTS = {         # code/SA_RRG.py's constants on the notebook's graph (nb:456-459)
+    "n": 1000,             # nb:456
+    "deg": 2.0,            # nb:459 (one mean degree; prob = deg/(n-1), nb:280)
+    "p": 1,                # nb:466
+    "c": 1,                # nb:467
+    "par_a": 1.0005,       # code/SA_RRG.py:49
     "par_b": 1.0005,       # :50
     "N_stat": 5,           # :52
 }
@@ -83,6 +96,15 @@ def build_parser():
     sa.add_argument("--max-steps", type=int, default=None, help="proposal cap per replica (the script's is 2n^3)")
     sa.add_argument("--max-seconds", type=float, default=None)
     _common(sa)
+    se = sub.add_parser("sa-er", help="code/SA_RRG.py's loop on an Erdos-Renyi graph")
+    for k, v in SA_ER_DEFAULTS.items():
+        se.add_argument(f"--{k}", type=type(v), default=v)
+    se.add_argument("--mode", choices=("auto", "lightcone", "rollout"), default="auto")
+    se.add_argument("--keep-isolated", action="store_true",
+                    help="keep degree-0 nodes (the notebook drops and relabels them, nb:283-291)")
+    se.add_argument("--max-steps", type=int, default=None, help="proposal cap per replica (the script's is 2n^3)")
+    se.add_argument("--max-seconds", type=float, default=None)
+    _common(se)
     hp = sub.add_parser("hpr", help="code/HPR_pytorch_RRG.py")
     for k, v in HPR_DEFAULTS.items():
         hp.add_argument(f"--{k}", type=(int if k == "lmbd_in" else type(v)), default=v)
@@ -164,6 +186,23 @@ def run_sa(a):
     return res
 
 
+def run_sa_er(a):
+    from .sa_er import sa_er_run
+    R = a.replicas if a.replicas is not None else a.N_stat
+    gs = a.graph_seed if a.graph_seed is not None else a.seed
+    _devices(a.gpus)                        # one graph shared by every replica: the current device
+    t0 = time.time()
+    res = sa_er_run(a.n, a.deg / (a.n - 1), a.p, a.c, par_a=a.par_a, par_b=a.par_b, N_stat=R, seed=a.seed,
+                    graph_seed=gs, drop_isolated=not a.keep_isolated, max_steps=a.max_steps,
+                    max_seconds=a.max_seconds, mode=a.mode)
+    out = a.out or f"SA_ER_p{a.p}.npz"
+    np.savez(out, **res)
+    print(f"sa-er: {R} replicas on {res['row_ptr'].shape[0] - 1} nodes ({int(res['n_iso'])} isolated dropped), "
+          f"num_steps {res['num_steps'].astype(np.int64).tolist()}, "
+          f"mag_reached {np.round(res['mag_reached'], 4).tolist()}, {time.time() - t0:.1f} s -> {out}", flush=True)
+    return res
+
+
 def run_hpr(a):
     import torch
     from .graph import random_regular_edges
@@ -206,7 +245,7 @@ def run_bdcm(a):
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return {"sa": run_sa, "hpr": run_hpr, "bdcm": run_bdcm}[a.cmd](a)
+    return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm}[a.cmd](a)
 
 
 if __name__ == "__main__":

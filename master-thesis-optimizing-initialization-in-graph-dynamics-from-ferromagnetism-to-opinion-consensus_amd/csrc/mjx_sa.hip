@@ -22,7 +22,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include "mjx_mt.h"
+#include "mjx_sa_core.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -176,45 +176,7 @@ __global__ void k_sa_init_state(int64_t n, int64_t R, double a0, double b0,
 // memory mt[r*624 + k].  A lane that runs out of words gets its state twisted
 // cooperatively by its whole wave through a 624-word LDS buffer.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t ld_nc(const uint32_t* p) {
-    // bypass the CU's L1: the words may have been rewritten by this wave's
-    // own cooperative twist earlier in this launch
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ void coop_twist(uint32_t* __restrict__ g, uint32_t* buf, int lane) {
-    for (int k = lane; k < MT_N; k += 64) buf[k] = ld_nc(g + k);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    lds_twist(buf, lane);
-    for (int k = lane; k < MT_N; k += 64) g[k] = buf[k];
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-struct WaveMT {
-    uint32_t* mt;      // all replicas
-    uint32_t* buf;     // this wave's LDS twist buffer
-    int64_t r;
-    int idx;
-    int lane;
-    // wave-uniform call: lanes with want == false still participate
-    __device__ __forceinline__ uint32_t draw(bool want) {
-        const bool tw = want && idx >= MT_N;
-        u64 m = __ballot(tw);
-        const int64_t base = r - lane;
-        while (m) {
-            const int l = __ffsll((unsigned long long)m) - 1;
-            coop_twist(mt + (base + l) * MT_N, buf, lane);
-            m &= m - 1;
-        }
-        if (tw) idx = 0;
-        uint32_t y = 0;
-        if (want) y = mt_temper(ld_nc(mt + r * MT_N + idx++));
-        return y;
-    }
-};
-
+// (WaveMT, the in-step MT19937 draw: mjx_sa_core.h)
 __global__ void __launch_bounds__(kBlock) k_sa_propose(int64_t n, int64_t R, int64_t W, u64* __restrict__ s,
                                                        mjx_sa_state st, int64_t step) {
     __shared__ uint32_t twist_buf[kBlock / 64][MT_N];
@@ -223,25 +185,12 @@ __global__ void __launch_bounds__(kBlock) k_sa_propose(int64_t n, int64_t R, int
     const bool live = r < R;
     const bool active = live && st.done[r] == 0;
     WaveMT g{st.mt, twist_buf[threadIdx.x >> 6], r, live ? st.mt_idx[r] : MT_N, lane};
-    // randint(low=0, high=n): numpy legacy masked rejection
-    const uint64_t rng = (uint64_t)(n - 1);
-    uint32_t mask = (uint32_t)rng;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-    bool pending = active && rng > 0;
+    // randint(low=0, high=n), then rand()
     uint32_t i = 0;
-    while (__ballot(pending)) {
-        uint32_t y = g.draw(pending);
-        if (pending) {
-            uint32_t v = y & mask;
-            if (v <= (uint32_t)rng) { i = v; pending = false; }
-        }
-    }
-    // rand()
-    uint32_t w1 = g.draw(active);
-    uint32_t w2 = g.draw(active);
+    double u = 0.0;
+    g.propose(active, n, i, u);
     if (live) st.mt_idx[r] = g.idx;
     if (active) {
-        const double u = mt_double(w1, w2);
         const u64 bit = 1ull << (r & 63);
         const u64 old = atomicXor((unsigned long long*)&s[(int64_t)i * W + (r >> 6)], (unsigned long long)bit);
         st.prop_i[r] = (int32_t)i;
@@ -266,19 +215,11 @@ __global__ void __launch_bounds__(kBlock) k_sa_accept(int64_t n, int64_t R, int6
     const int64_t sum_old = st.sum_end[r];                      // sum(s_endstate(s))
     const double a = st.a[r], b = st.b[r];
     const double si = (double)st.prop_s[r];
-    // delta_H = (-2*a*s0[i] + b*(sum(s_end1) - sum(s_end2)))/n   (code/SA_RRG.py:37)
-    const double t1 = (-2.0 * a) * si;
-    const double t2 = b * (double)(sum_old - sum_new);
-    const double dE = (t1 + t2) / (double)n;
-    // prob_accept = min([1, np.exp(-delta_H)])                 (code/SA_RRG.py:75)
-    const double e = exp(-dE);
-    const double prob = (e < 1.0) ? e : 1.0;
-    const double u = st.prop_u[r];
-    const bool acc = u < prob;                                  // (code/SA_RRG.py:76)
-    if (st.tr_tie && e < 1.0) {
-        const double gap = fabs(u - e);
-        if (gap <= 4.0 * (nextafter(e, 2.0) - e)) st.tr_tie[r] += 1;
-    }
+    // delta_H, prob_accept = min([1, np.exp(-delta_H)]), u < prob_accept (code/SA_RRG.py:37,75-76)
+    const SaVerdict vd = sa_metropolis(a, b, si, sum_old, sum_new, n, st.prop_u[r]);
+    const double dE = vd.dE;
+    const bool acc = vd.acc;
+    if (st.tr_tie && vd.tie) st.tr_tie[r] += 1;
     int64_t sum_cur = sum_old;
     if (acc) {
         sum_cur = sum_new;
@@ -286,17 +227,16 @@ __global__ void __launch_bounds__(kBlock) k_sa_accept(int64_t n, int64_t R, int6
         const int32_t i = st.prop_i[r];
         atomicXor((unsigned long long*)&s[(int64_t)i * W + (r >> 6)], (unsigned long long)(1ull << (r & 63)));
     }
-    // annealing schedule (code/SA_RRG.py:80-81)
+    // annealing schedule, step count, termination (code/SA_RRG.py:80-85)
     double an = a, bn = b;
-    if (a < a_cap) an = par_a * a;
-    if (b < b_cap) bn = par_b * b;
+    int64_t t = st.t[r];
+    int done = 0;
+    sa_advance(an, bn, t, done, sum_cur, n, par_a, par_b, a_cap, b_cap, t_cap);
     st.a[r] = an;
     st.b[r] = bn;
-    const int64_t t = st.t[r] + 1;                               // (code/SA_RRG.py:82)
     st.t[r] = t;
     st.sum_end[r] = sum_cur;
-    if (t > t_cap) st.done[r] = 2;                              // m_final = 2 (code/SA_RRG.py:84)
-    else if (sum_cur == n) st.done[r] = 1;                      // m(s_endstate(s)) == 1
+    if (done) st.done[r] = done;
     if (st.tr_acc) st.tr_acc[step * R + r] = acc ? 1 : 0;
     if (st.tr_sum) st.tr_sum[step * R + r] = sum_cur;
     if (st.tr_dE) st.tr_dE[step * R + r] = dE;
@@ -335,10 +275,6 @@ struct LcLevels {
     int tab;                 // slot offset of the ball table (node ids | adjacency rows | candidate entries)
     int ball;                // table capacity: nodes of the radius-T ball (d-regular bound)
 };
-
-__device__ __forceinline__ u64 ld_word(const u64* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <int D>
 __device__ __forceinline__ int lc_nbrs(const int32_t* __restrict__ adj, int d, int32_t v, int32_t* k) {
@@ -956,9 +892,6 @@ __global__ void __launch_bounds__(64) k_sa_lightcone(const int32_t* __restrict__
     int64_t t = live ? st.t[r] : 0, sum_end = live ? st.sum_end[r] : 0;
     int done = live ? st.done[r] : 1;
     int ties = 0;
-    const uint64_t rng = (uint64_t)(n - 1);
-    uint32_t mask = (uint32_t)rng;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
     // tape mode: proposals k+1 and k+2 are held in registers while step k runs
     // (tape rows come three steps ahead); with the batched evaluation the
     // adjacency rows of i_{k+1}'s neighbours and of i_{k+2} are loaded during
@@ -1006,19 +939,8 @@ __global__ void __launch_bounds__(64) k_sa_lightcone(const int32_t* __restrict__
                 n2u = tape_u[r * st.tape_cap + step + 3];
             }
         } else {
-            // randint(low=0, high=n) (code/SA_RRG.py:73): numpy legacy masked rejection
-            bool pending = active && rng > 0;
-            while (__ballot(pending)) {
-                const uint32_t y = g.draw(pending);
-                if (pending) {
-                    const uint32_t v = y & mask;
-                    if (v <= (uint32_t)rng) { i = v; pending = false; }
-                }
-            }
-            // rand() (code/SA_RRG.py:76)
-            const uint32_t w1 = g.draw(active);
-            const uint32_t w2 = g.draw(active);
-            u = mt_double(w1, w2);
+            // randint(low=0, high=n), then rand() (code/SA_RRG.py:73,76)
+            g.propose(active, n, i, u);
         }
         if (active) {
             int cnt[LC_MAXT + 1];
@@ -1051,14 +973,10 @@ __global__ void __launch_bounds__(64) k_sa_lightcone(const int32_t* __restrict__
             }
             const int64_t sum_new = sum_end + ds;
             // delta_H (code/SA_RRG.py:37), same operation order, no contraction
-            const double si = old_i ? 1.0 : -1.0;
-            const double t1 = (-2.0 * a) * si;
-            const double t2 = b * (double)(sum_end - sum_new);
-            const double dE = (t1 + t2) / (double)n;
-            const double e = exp(-dE);
-            const double prob = (e < 1.0) ? e : 1.0;                 // (code/SA_RRG.py:75)
-            const bool acc = u < prob;                               // (code/SA_RRG.py:76)
-            if (e < 1.0 && fabs(u - e) <= 4.0 * (nextafter(e, 2.0) - e)) ++ties;
+            const SaVerdict vd = sa_metropolis(a, b, old_i ? 1.0 : -1.0, sum_end, sum_new, n, u);
+            const double dE = vd.dE;
+            const bool acc = vd.acc;                                 // (code/SA_RRG.py:75-76)
+            if (vd.tie) ++ties;
             if (acc) {                                               // (code/SA_RRG.py:77)
                 for (int lv = 0; lv <= T; ++lv) {
                     const uint32_t* lst = lists + L.off[lv] * 64;
@@ -1071,11 +989,7 @@ __global__ void __launch_bounds__(64) k_sa_lightcone(const int32_t* __restrict__
                 }
                 sum_end = sum_new;
             }
-            if (a < a_cap) a = par_a * a;                            // (code/SA_RRG.py:80-81)
-            if (b < b_cap) b = par_b * b;
-            t += 1;                                                  // (code/SA_RRG.py:82)
-            if (t > t_cap) done = 2;                                 // (code/SA_RRG.py:84)
-            else if (sum_end == n) done = 1;                         // m(s_endstate(s)) == 1
+            sa_advance(a, b, t, done, sum_end, n, par_a, par_b, a_cap, b_cap, t_cap);   // (code/SA_RRG.py:80-85)
             if (st.tr_i) st.tr_i[step * R + r] = (int32_t)i;
             if (st.tr_acc) st.tr_acc[step * R + r] = acc ? 1 : 0;
             if (st.tr_sum) st.tr_sum[step * R + r] = sum_end;
@@ -2125,12 +2039,10 @@ static int sa_init_finish(const int32_t* adj, int64_t n, int d, int T, int64_t R
     int rc = st.rep_graph ? mjx_rollout_ell_rp_multi(adj, n, d, R, st.rep_graph, s, tmp1, tmp2, T, st.cnt, stream)
                           : mjx_rollout_ell_rp(adj, n, d, W, s, tmp1, tmp2, T, st.cnt, stream);
     if (rc) return rc;
-    k_sa_init_state<<<(unsigned)((R + 255) / 256), 256, 0, hs>>>(n, R, a0, b0, st.cnt, st);
-    MJX_LAUNCH_CHECK("k_sa_init_state");
-    return MJX_OK;
+    return sa_init_state(n, R, a0, b0, st, hs);
 }
 
-static bool sa_state_complete(const mjx_sa_state& st) {
+bool mjx::sa_state_complete(const mjx_sa_state& st) {
     return st.mt && st.mt_idx && st.a && st.b && st.t && st.sum_end && st.done && st.prop_i && st.prop_s &&
            st.prop_u && st.cnt;
 }
@@ -2146,10 +2058,8 @@ extern "C" int mjx_sa_init_mt(const int32_t* adj, int64_t n, int d, int p, int c
     const int64_t W = (R + 63) / 64;
     const int T = p + c - 1;
     if (T >= 2 && !tmp2) return MJX_EINVAL;
-    // lane per replica: each lane continues its own stream from its own index
-    k_sa_init_draw<<<(unsigned)W, 64, 0, as_stream(stream)>>>(n, R, W, nullptr, (u64*)s, st.mt, st.mt_idx, mt_in,
-                                                               idx_in);
-    MJX_LAUNCH_CHECK("k_sa_init_draw");
+    const int rc = sa_draw_s0_mt(n, R, mt_in, idx_in, s, st, as_stream(stream));
+    if (rc) return rc;
     return sa_init_finish(adj, n, d, T, R, W, a0, b0, s, tmp1, tmp2, st, stream);
 }
 
@@ -2165,7 +2075,14 @@ extern "C" int mjx_sa_init(const int32_t* adj, int64_t n, int d, int p, int c, i
     const int64_t W = (R + 63) / 64;
     const int T = p + c - 1;
     if (T >= 2 && !tmp2) return MJX_EINVAL;
-    hipStream_t hs = as_stream(stream);
+    const int rc = sa_draw_s0(n, R, seeds, s, tmp1, st, as_stream(stream));
+    if (rc) return rc;
+    return sa_init_finish(adj, n, d, T, R, W, a0, b0, s, tmp1, tmp2, st, stream);
+}
+
+int mjx::sa_draw_s0(int64_t n, int64_t R, const uint32_t* seeds, uint64_t* s, uint64_t* tmp1, const mjx_sa_state& st,
+                    hipStream_t hs) {
+    const int64_t W = (R + 63) / 64;
     // s0 draws, wave per replica, through node-packed rows in tmp1 (n*W words
     // hold G word columns of 64 rows of ceil(n/64) words each)
     const int64_t nw = (n + 63) / 64;
@@ -2184,7 +2101,36 @@ extern "C" int mjx_sa_init(const int32_t* adj, int64_t n, int d, int p, int c, i
             MJX_LAUNCH_CHECK("k_np_to_rp");
         }
     }
-    return sa_init_finish(adj, n, d, T, R, W, a0, b0, s, tmp1, tmp2, st, stream);
+    return MJX_OK;
+}
+
+int mjx::sa_draw_s0_mt(int64_t n, int64_t R, const uint32_t* mt_in, const int32_t* idx_in, uint64_t* s,
+                       const mjx_sa_state& st, hipStream_t hs) {
+    const int64_t W = (R + 63) / 64;
+    // lane per replica: each lane continues its own stream from its own index
+    k_sa_init_draw<<<(unsigned)W, 64, 0, hs>>>(n, R, W, nullptr, (u64*)s, st.mt, st.mt_idx, mt_in, idx_in);
+    MJX_LAUNCH_CHECK("k_sa_init_draw");
+    return MJX_OK;
+}
+
+int mjx::sa_init_state(int64_t n, int64_t R, double a0, double b0, const mjx_sa_state& st, hipStream_t hs) {
+    k_sa_init_state<<<(unsigned)((R + 255) / 256), 256, 0, hs>>>(n, R, a0, b0, st.cnt, st);
+    MJX_LAUNCH_CHECK("k_sa_init_state");
+    return MJX_OK;
+}
+
+int mjx::sa_propose(int64_t n, int64_t R, uint64_t* s, const mjx_sa_state& st, int64_t step, hipStream_t hs) {
+    k_sa_propose<<<(unsigned)((R + kBlock - 1) / kBlock), kBlock, 0, hs>>>(n, R, (R + 63) / 64, (u64*)s, st, step);
+    MJX_LAUNCH_CHECK("k_sa_propose");
+    return MJX_OK;
+}
+
+int mjx::sa_accept(int64_t n, int64_t R, uint64_t* s, const mjx_sa_state& st, int64_t step, double par_a,
+                   double par_b, double a_cap, double b_cap, int64_t t_cap, hipStream_t hs) {
+    k_sa_accept<<<(unsigned)((R + kBlock - 1) / kBlock), kBlock, 0, hs>>>(n, R, (R + 63) / 64, (u64*)s, st, step,
+                                                                         par_a, par_b, a_cap, b_cap, t_cap);
+    MJX_LAUNCH_CHECK("k_sa_accept");
+    return MJX_OK;
 }
 
 extern "C" int mjx_sa_steps(const int32_t* adj, int64_t n, int d, int p, int c, int64_t R, uint64_t* s,
@@ -2199,16 +2145,13 @@ extern "C" int mjx_sa_steps(const int32_t* adj, int64_t n, int d, int p, int c, 
     const int T = p + c - 1;
     if (T >= 2 && !tmp2) return MJX_EINVAL;
     hipStream_t hs = as_stream(stream);
-    const unsigned gridR = (unsigned)((R + kBlock - 1) / kBlock);
     for (int64_t k = 0; k < nsteps; ++k) {
-        k_sa_propose<<<gridR, kBlock, 0, hs>>>(n, R, W, (u64*)s, st, k);
-        MJX_LAUNCH_CHECK("k_sa_propose");
+        if (int rc = sa_propose(n, R, s, st, k, hs)) return rc;
         MJX_HIP(hipMemsetAsync(st.cnt, 0, (size_t)R * sizeof(unsigned long long), hs), "sa_steps memset");
         int rc = st.rep_graph ? mjx_rollout_ell_rp_multi(adj, n, d, R, st.rep_graph, s, tmp1, tmp2, T, st.cnt, stream)
                               : mjx_rollout_ell_rp(adj, n, d, W, s, tmp1, tmp2, T, st.cnt, stream);
         if (rc) return rc;
-        k_sa_accept<<<gridR, kBlock, 0, hs>>>(n, R, W, (u64*)s, st, k, par_a, par_b, a_cap, b_cap, t_cap);
-        MJX_LAUNCH_CHECK("k_sa_accept");
+        if ((rc = sa_accept(n, R, s, st, k, par_a, par_b, a_cap, b_cap, t_cap, hs))) return rc;
     }
     return MJX_OK;
 }

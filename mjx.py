@@ -16,7 +16,7 @@ _sys.modules["mjx"] = _mod
 _spec.loader.exec_module(_mod)
 
 if __name__ == "__main__":
-    # python -m mjx sa|hpr|bdcm ...: the reference's experiments with its
+    # python -m mjx sa|sa-er|hpr|bdcm ...: the reference's experiments with its
     # constants as flags (package module cli.py)
     import importlib as _il
     _il.import_module("mjx.cli").main(_sys.argv[1:])
