@@ -654,6 +654,48 @@ int mjx_bdcm_edge_obs(const double* chi, const int32_t* edges, const int32_t* de
  * work: 256 doubles of device scratch. */
 int mjx_sum_f64(const double* x, int64_t n, int take_log, double* work, double* out, void* stream);
 
+/* ---- BDCM on a batch of G graphs as one disjoint union ---- */
+/*
+ * Instance g owns the contiguous rows [row_off[g], row_off[g] + 2 E_g) of one
+ * chi[sum 2 E_g][4^T] and keeps the notebook's layout inside its block (local
+ * row r < E_g is u -> v, r + E_g is v -> u), so the reverse of a union row is
+ * not "row + E_total": the edge observables take both rows explicitly.  Class D
+ * of the union is the union of the instances' classes D, rows / inc hold union
+ * rows and inst[m] the instance of every item.  All instances share p, c,
+ * attr_value, damp, eps and lambda.  Per-instance control is ctl[G][4] int64,
+ * the block of mjx_bdcm_iter_* once per instance: [0] delta bits of the
+ * running sweep, [1] stop flag, [2] sweeps done, [3] delta bits of the last
+ * completed sweep.
+ */
+#define MJX_BDCM_GATE 1  /* items of an instance with ctl[g][1] != 0 are left untouched */
+#define MJX_BDCM_DELTA 2 /* max |new - old| of an item's row -> atomic max into ctl[g][0] */
+/* mjx_bdcm_update_class for a union class; item e belongs to instance inst[e].
+ * flags: MJX_BDCM_GATE -- neither the compute nor the commit launch touches a
+ * row of a stopped instance (bit for bit); MJX_BDCM_DELTA -- the maximum of
+ * |new - old| over an item's row goes into its own instance's ctl[g][0] only
+ * (a NaN wins).  inst and ctl are required with either flag (MJX_EINVAL) and
+ * unused without.  w_dev, scratch, scratch_bytes and the chunked launches of a
+ * class beyond the LDS budget as in mjx_bdcm_update_class. */
+int mjx_bdcm_update_class_batch(double* chi, const int32_t* rows, const int32_t* inc, const int32_t* inst, int64_t m,
+                                int D, int p, int c, int attr_value, double lmbd, double damp, double eps, double* upd,
+                                long long* ctl, int flags, const double* w_dev, void* scratch, int64_t scratch_bytes,
+                                void* stream);
+/* mjx_bdcm_iter_begin / _end applied to each of the G control blocks
+ * independently (one thread per instance). */
+int mjx_bdcm_iter_begin_batch(long long* ctl, int64_t G, void* stream);
+int mjx_bdcm_iter_end_batch(long long* ctl, int64_t G, double eps, int64_t t_max, void* stream);
+/* mjx_bdcm_edge_obs with the two rows of union edge e given as fwd_row[e]
+ * (u -> v) and rev_row[e] (v -> u); edges[2 E_total] and deg[] hold union node
+ * ids.  The same summation order per edge. */
+int mjx_bdcm_edge_obs_batch(const double* chi, const int32_t* fwd_row, const int32_t* rev_row, const int32_t* edges,
+                            const int32_t* deg, int64_t E_total, int p, int c, int attr_value, double eps, double* zij,
+                            double* m_term, void* stream);
+/* out[g] = sum (take_log: sum of logs) of x[seg_ptr[g] : seg_ptr[g+1]], g < G,
+ * with the bits mjx_sum_f64 gives on that segment alone; an empty segment
+ * gives 0.  seg_ptr[G+1] int64 on the device; work: G*256 doubles. */
+int mjx_segsum_f64(const double* x, const int64_t* seg_ptr, int64_t G, int take_log, double* work, double* out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,9 +18,12 @@ from .sa import SAReplicas, E_delta, sa_run, schedule_constants
 from .sa_er import SAReplicasER, sa_er_run
 from .hpr import HPRPlan, HPRState, HPr_dp, marginals_comp, new_biases_i, hpr_run
 from .hpr_er import HPRERPlan, HPr_dp_er, marginals_comp_er, hpr_er_plan, hpr_er_run
+from .bdcm import plan_indices as bdcm_plan_indices
 from .bdcm import (BDCMPlan, bdcm_er_plan, BDCM_ER, bdcm_leaf_reset, Zij, Zi_ER, phi_BP_GENERAL_ER,
                    avg_m_init_GENERAL_ER, BDCM_entropy_procedure_GENERAL_ER, bdcm_er_run)
 from .bdcm import converge as bdcm_converge
+from .bdcm_batch import (BDCMBatch, bdcm_batch_layout, BDCM_ER_batch, bdcm_leaf_reset_batch, bdcm_converge_batch,
+                         bdcm_partition_batch, bdcm_observables_batch, BDCM_entropy_procedure_batch)
 from . import drop_in  # reference-signature HPR drop-ins (code/HPR_pytorch_RRG.py)
 
 __all__ = [
@@ -31,8 +34,10 @@ __all__ = [
     "SAReplicasER", "sa_er_run",
     "HPRPlan", "HPRState", "HPr_dp", "marginals_comp", "new_biases_i", "hpr_run",
     "HPRERPlan", "HPr_dp_er", "marginals_comp_er", "hpr_er_plan", "hpr_er_run",
-    "BDCMPlan", "bdcm_er_plan", "BDCM_ER", "bdcm_converge", "bdcm_leaf_reset", "Zij", "Zi_ER", "phi_BP_GENERAL_ER",
+    "BDCMPlan", "bdcm_plan_indices", "bdcm_er_plan", "BDCM_ER", "bdcm_converge", "bdcm_leaf_reset", "Zij", "Zi_ER", "phi_BP_GENERAL_ER",
     "avg_m_init_GENERAL_ER", "BDCM_entropy_procedure_GENERAL_ER", "bdcm_er_run", "drop_in",
+    "BDCMBatch", "bdcm_batch_layout", "BDCM_ER_batch", "bdcm_leaf_reset_batch", "bdcm_converge_batch",
+    "bdcm_partition_batch", "bdcm_observables_batch", "BDCM_entropy_procedure_batch",
 ]
 
 

@@ -120,6 +120,12 @@ SIGNATURES = {
                         c_vp],
     "mjx_bdcm_edge_obs": [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp],
     "mjx_sum_f64": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp],
+    "mjx_bdcm_update_class_batch": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl,
+                                    c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp],
+    "mjx_bdcm_iter_begin_batch": [c_vp, c_i64, c_vp],
+    "mjx_bdcm_iter_end_batch": [c_vp, c_i64, c_dbl, c_i64, c_vp],
+    "mjx_bdcm_edge_obs_batch": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp],
+    "mjx_segsum_f64": [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "mjx_last_hip_error": ctypes.c_char_p,
              "mjx_sa_lightcone_lds": c_i64, "mjx_sa_lds_bytes": c_i64, "mjx_sa_lds_plan": c_i64, "mjx_bdcm_lds_bytes": c_i64, "mjx_bdcm_scratch_bytes": c_i64,
@@ -130,6 +136,7 @@ _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "
 MJX_OK, MJX_EINVAL, MJX_EHIP, MJX_ERANGE = 0, 1, 2, 3      # status codes (include/mjx.h)
 MJX_I8, MJX_I32, MJX_I64 = 1, 4, 8
 MJX_F32, MJX_F64 = 104, 108
+MJX_BDCM_GATE, MJX_BDCM_DELTA = 1, 2                        # flags of mjx_bdcm_update_class_batch
 
 
 class MjxSaState(ctypes.Structure):

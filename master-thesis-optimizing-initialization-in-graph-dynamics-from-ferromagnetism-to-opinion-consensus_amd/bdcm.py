@@ -14,6 +14,8 @@ explicit arguments:
   avg_m_init_GENERAL_ER(chi, plan, p, c, attr_value, epsilon)        nb:379-392
   BDCM_entropy_procedure_GENERAL_ER(chi, plan, lambdas, ...)         nb:394-452
   bdcm_er_run(n, deg, ...)                                           the notebook cell's main loop (nb:455-515)
+                                                                     (batch=B: B graphs at a time as one union
+                                                                     graph, module bdcm_batch)
 
 ``chi`` is the notebook's message array in float64, shape (2E, 4^T) or
 (2E,) + (2,)*2T, resident on the device and updated in place like the
@@ -35,6 +37,58 @@ def _i32(a, dev):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))).to(dev)
 
 
+def plan_indices(edges, row_ptr, col):
+    """Host index arrays of one core graph (numpy only, no GPU): dict with
+    edges (E, 2), row_ptr, col, deg, n_core, E, edge_classes = [(D, rows[m],
+    inc[m, D])] in ascending D (rows of the messages a -> b with deg(a) - 1 = D
+    and the rows of their D incoming messages k -> a, nb:312-318) and
+    node_classes = [(D, nodes[m], inc[m, D])] (nb:211-276)."""
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    rp = np.asarray(row_ptr, dtype=np.int64)
+    cl = np.asarray(col, dtype=np.int64)
+    n = rp.size - 1
+    E = e.shape[0]
+    if n < 1 or cl.size != 2 * E or rp[0] != 0 or rp[-1] != cl.size:
+        raise ValueError("CSR must hold both directions of every edge of the edge list")
+    deg = np.diff(rp)
+    if deg.min() < 1:
+        raise ValueError("remove isolated nodes first (nb:283-291) and pass their number as n_iso")
+    keys = np.concatenate([e[:, 0] * n + e[:, 1], e[:, 1] * n + e[:, 0]])
+    order = np.argsort(keys, kind="stable")
+    sk = keys[order]
+    if sk.size > 1 and np.any(sk[1:] == sk[:-1]):
+        raise ValueError("multi-edge in the edge list")
+
+    def row_of(x, y):
+        k = (np.asarray(x) * n + np.asarray(y)).reshape(-1)
+        pos = np.minimum(np.searchsorted(sk, k), sk.size - 1)
+        if k.size and np.any(sk[pos] != k):
+            raise ValueError("neighbour lists inconsistent with the edge list")
+        return order[pos]
+
+    full = np.concatenate([e, e[:, ::-1]])
+    cls = deg[full[:, 0]] - 1                               # edges_degree (nb:312-313)
+    edge_classes = []                                       # ascending D: Gauss-Seidel order (nb:138)
+    for D in np.unique(cls).tolist():
+        rows = np.flatnonzero(cls == D)
+        a, b = full[rows, 0], full[rows, 1]
+        nb = cl[rp[a][:, None] + np.arange(D + 1)[None, :]]
+        keep = nb != b[:, None]
+        if not np.all(keep.sum(axis=1) == D):
+            raise ValueError("graph is not simple")
+        kn = nb[keep].reshape(rows.size, D)
+        inc = row_of(kn, np.broadcast_to(a[:, None], kn.shape)) if D else np.zeros(0, np.int64)
+        edge_classes.append((int(D), rows, inc.reshape(rows.size, D)))
+    node_classes = []
+    for D in np.unique(deg).tolist():
+        nodes = np.flatnonzero(deg == D)
+        nb = cl[rp[nodes][:, None] + np.arange(D)[None, :]]
+        inc = row_of(nb, np.broadcast_to(nodes[:, None], nb.shape))
+        node_classes.append((int(D), nodes, inc.reshape(nodes.size, D)))
+    return {"edges": e, "row_ptr": rp, "col": cl, "deg": deg, "n_core": int(n), "E": int(E),
+            "edge_classes": edge_classes, "node_classes": node_classes}
+
+
 class BDCMPlan:
     """Device-resident index arrays of an ER core graph (isolated nodes removed,
     nb:283-291) for the BDCM kernels.
@@ -46,55 +100,18 @@ class BDCMPlan:
     removed (they enter phi and m_init, nb:376, 392)."""
 
     def __init__(self, edges, row_ptr, col, n_total=None, n_iso=0):
-        e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
-        rp = np.asarray(row_ptr, dtype=np.int64)
-        cl = np.asarray(col, dtype=np.int64)
-        n = rp.size - 1
-        E = e.shape[0]
-        if n < 1 or cl.size != 2 * E or rp[0] != 0 or rp[-1] != cl.size:
-            raise ValueError("CSR must hold both directions of every edge of the edge list")
-        deg = np.diff(rp)
-        if deg.min() < 1:
-            raise ValueError("remove isolated nodes first (nb:283-291) and pass their number as n_iso")
-        keys = np.concatenate([e[:, 0] * n + e[:, 1], e[:, 1] * n + e[:, 0]])
-        order = np.argsort(keys, kind="stable")
-        sk = keys[order]
-        if sk.size > 1 and np.any(sk[1:] == sk[:-1]):
-            raise ValueError("multi-edge in the edge list")
-
-        def row_of(x, y):
-            k = (np.asarray(x) * n + np.asarray(y)).reshape(-1)
-            pos = np.minimum(np.searchsorted(sk, k), sk.size - 1)
-            if k.size and np.any(sk[pos] != k):
-                raise ValueError("neighbour lists inconsistent with the edge list")
-            return order[pos]
-
-        full = np.concatenate([e, e[:, ::-1]])
-        cls = deg[full[:, 0]] - 1                               # edges_degree (nb:312-313)
+        h = self.host = plan_indices(edges, row_ptr, col)
+        e, deg = h["edges"], h["deg"]
         dev = _device.require_gpu()
         self.device = dev
-        self.n_core, self.E = int(n), int(E)
+        self.n_core, self.E = h["n_core"], h["E"]
         self.n_iso = int(n_iso)
         self.n = int(n_total) if n_total is not None else self.n_core + self.n_iso
         self.edges_host, self.deg_host = e, deg
-        self.row_ptr_host, self.col_host = rp, cl
-        self.edge_classes = []                                  # ascending D: Gauss-Seidel order (nb:138)
-        for D in np.unique(cls).tolist():
-            rows = np.flatnonzero(cls == D)
-            a, b = full[rows, 0], full[rows, 1]
-            nb = cl[rp[a][:, None] + np.arange(D + 1)[None, :]]
-            keep = nb != b[:, None]
-            if not np.all(keep.sum(axis=1) == D):
-                raise ValueError("graph is not simple")
-            kn = nb[keep].reshape(rows.size, D)
-            inc = row_of(kn, np.broadcast_to(a[:, None], kn.shape)) if D else np.zeros(0, np.int64)
-            self.edge_classes.append((int(D), _i32(rows, dev), _i32(inc, dev), int(rows.size)))
-        self.node_classes = []
-        for D in np.unique(deg).tolist():
-            nodes = np.flatnonzero(deg == D)
-            nb = cl[rp[nodes][:, None] + np.arange(D)[None, :]]
-            inc = row_of(nb, np.broadcast_to(nodes[:, None], nb.shape))
-            self.node_classes.append((int(D), _i32(nodes, dev), _i32(inc, dev), int(nodes.size)))
+        self.row_ptr_host, self.col_host = h["row_ptr"], h["col"]
+        self.edge_classes = [(D, _i32(rows, dev), _i32(inc, dev), int(rows.size)) for D, rows, inc in h["edge_classes"]]
+        self.node_classes = [(D, _i32(nodes, dev), _i32(inc, dev), int(nodes.size))
+                             for D, nodes, inc in h["node_classes"]]
         self.edges = _i32(e, dev)
         self.deg = _i32(deg, dev)
         self._work = torch.empty(256, dtype=torch.float64, device=dev)
@@ -368,12 +385,14 @@ def BDCM_entropy_procedure_GENERAL_ER(chi, plan, lambdas, T_max=1300, p=1, c=1, 
 
 
 def bdcm_er_run(n=1000, deg=(1.0, 1.5, 2.0), num_rep=3, p=1, c=1, eps=1e-6, damppar=0.1, attr_value=1,
-                epsilon=0.0, T_max=1300, a=12, dl=0.1, seed=0, verbose=False):
+                epsilon=0.0, T_max=1300, a=12, dl=0.1, seed=0, verbose=False, batch=0):
     """The notebook's experiment (nb:455-515) on this package's own ER graphs:
     for every mean degree and replica a fresh G(n, deg/(n-1)) core graph,
     uniform random normalised messages, and the lambda sweep
     linspace(0, a, a/dl + 1).  Returns the arrays of the (commented) np.savez
-    of nb:515 with the same keys."""
+    of nb:515 with the same keys.  ``batch`` = B > 0: the same graphs and
+    messages (drawn in the same order from the one generator) run B at a time
+    as one union graph (``bdcm_batch``); the returned arrays are the same."""
     deg = np.atleast_1d(np.asarray(deg, dtype=np.float64))
     prob = deg / (n - 1)
     lambdas = np.linspace(0, a, int(a / dl + 1))
@@ -383,6 +402,18 @@ def bdcm_er_run(n=1000, deg=(1.0, 1.5, 2.0), num_rep=3, p=1, c=1, eps=1e-6, damp
         out[k] = np.zeros((deg.size, num_rep))
     rng = np.random.default_rng(seed)
     T = p + c
+    kw = dict(T_max=T_max, p=p, c=c, attr_value=attr_value, eps=eps, damppar=damppar, epsilon=epsilon, verbose=verbose)
+    pending = []                             # (i, r, plan, chi0 on the host) of a group still to run
+
+    def run_group():
+        from .bdcm_batch import BDCMBatch, BDCM_entropy_procedure_batch
+        bt = BDCMBatch([pl for _, _, pl, _ in pending], p, c)
+        res = BDCM_entropy_procedure_batch(bt.chi_from([x for _, _, _, x in pending]), bt, lambdas, **kw)
+        for (i, r, _, _), rs in zip(pending, res):
+            for k in ("m_init", "ent1", "ent"):
+                out[k][i, r] = rs[k]
+        pending.clear()
+
     for i in range(deg.size):
         for r in range(num_rep):
             plan = bdcm_er_plan(n, prob[i], seed=int(rng.integers(2 ** 63)))
@@ -391,10 +422,17 @@ def bdcm_er_run(n=1000, deg=(1.0, 1.5, 2.0), num_rep=3, p=1, c=1, eps=1e-6, damp
             out["mean_degrees_total"][i, r] = 2 * plan.E / n
             out["max_degrees"][i, r] = plan.deg_host.max()
             chi = rng.random((2 * plan.E, 4 ** T))
-            chi = torch.from_numpy(chi / chi.sum(axis=1, keepdims=True)).to(plan.device)
-            res = BDCM_entropy_procedure_GENERAL_ER(chi, plan, lambdas, T_max=T_max, p=p, c=c, attr_value=attr_value,
-                                                    eps=eps, damppar=damppar, epsilon=epsilon, verbose=verbose)
+            chi = chi / chi.sum(axis=1, keepdims=True)
+            if batch > 0:
+                pending.append((i, r, plan, chi))
+                if len(pending) == batch:
+                    run_group()
+                continue
+            chi = torch.from_numpy(chi).to(plan.device)
+            res = BDCM_entropy_procedure_GENERAL_ER(chi, plan, lambdas, **kw)
             for k in ("m_init", "ent1", "ent"):
                 out[k][i, r] = res[k]
+    if pending:
+        run_group()
     out.update(deg=deg, prob=prob, T_max=np.array(T_max), num_rep=np.array(num_rep))
     return out

@@ -117,6 +117,8 @@ def build_parser():
             bd.add_argument("--deg", type=float, nargs="+", default=list(v))
         else:        # a (the lambda range's end) may be given as a float too
             bd.add_argument(f"--{k}", type=float if k == "a" else type(v), default=v)
+    bd.add_argument("--batch", type=int, default=0,
+                    help="run that many graphs at a time as one union graph (0: one after the other); same output")
     _common(bd)
     return ap
 
@@ -236,7 +238,8 @@ def run_bdcm(a):
     _devices(a.gpus)                        # notebook-sized graphs: replicas run on the current device
     t0 = time.time()
     res = bdcm_er_run(n=a.n, deg=tuple(a.deg), num_rep=R, p=a.p, c=a.c, eps=a.eps, damppar=a.damppar,
-                      attr_value=a.attr_value, epsilon=a.epsilon, T_max=a.T_max, a=a.a, dl=a.dl, seed=a.seed)
+                      attr_value=a.attr_value, epsilon=a.epsilon, T_max=a.T_max, a=a.a, dl=a.dl, seed=a.seed,
+                      batch=a.batch)
     out = a.out or f"ER_p{a.p}.npz"
     save_bdcm_npz(out, res)
     print(f"bdcm: deg {list(a.deg)} x {R} replicas, {time.time() - t0:.1f} s -> {out}", flush=True)

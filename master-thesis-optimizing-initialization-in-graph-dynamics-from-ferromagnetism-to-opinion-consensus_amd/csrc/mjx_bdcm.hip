@@ -248,18 +248,12 @@ __device__ void build_table(const Geo& g, const double* __restrict__ chi, const 
 // damp >= 1 assigns normalize(chi2) (the leaf reset of nb:404-417 is class D = 0).
 // The count table lives in LDS, or (a class whose table exceeds the LDS budget)
 // in the global slab gtab, one table per workgroup of the launch; item e0 + blockIdx.x.
-__global__ void __launch_bounds__(256) k_bdcm_edge(const double* __restrict__ chi, const int32_t* __restrict__ rows,
-                                                  const int32_t* __restrict__ inc, Geo g, double w_plus,
-                                                  double w_minus, double eps, double damp, double* __restrict__ upd,
-                                                  int64_t e0, double* __restrict__ gtab,
-                                                  const long long* __restrict__ gate,
-                                                  const double* __restrict__ w_dev) {
-    if (gate && *gate) return;                 // a converged loop replays as no-ops
-    if (w_dev) {                               // lambda's weights from device memory (a captured loop)
-        w_plus = w_dev[0];
-        w_minus = w_dev[1];
-    }
-    extern __shared__ __align__(16) double sm[];
+// edge_item is the work of one workgroup (sm: its dynamic LDS), shared by the
+// single-plan kernel and the batch kernel.
+__device__ __forceinline__ void edge_item(const double* __restrict__ chi, const int32_t* __restrict__ rows,
+                                          const int32_t* __restrict__ inc, const Geo& g, double w_plus,
+                                          double w_minus, double eps, double damp, double* __restrict__ upd,
+                                          int64_t e0, double* __restrict__ gtab, double* sm) {
     double* M = sm;
     double* tab = gtab ? gtab + (size_t)blockIdx.x * g.XV * g.S : sm + (size_t)g.D * g.XV * g.XV;
     const int lane = threadIdx.x;
@@ -297,6 +291,40 @@ __global__ void __launch_bounds__(256) k_bdcm_edge(const double* __restrict__ ch
     }
 }
 
+__global__ void __launch_bounds__(256) k_bdcm_edge(const double* __restrict__ chi, const int32_t* __restrict__ rows,
+                                                  const int32_t* __restrict__ inc, Geo g, double w_plus,
+                                                  double w_minus, double eps, double damp, double* __restrict__ upd,
+                                                  int64_t e0, double* __restrict__ gtab,
+                                                  const long long* __restrict__ gate,
+                                                  const double* __restrict__ w_dev) {
+    if (gate && *gate) return;                 // a converged loop replays as no-ops
+    if (w_dev) {                               // lambda's weights from device memory (a captured loop)
+        w_plus = w_dev[0];
+        w_minus = w_dev[1];
+    }
+    extern __shared__ __align__(16) double sm[];
+    edge_item(chi, rows, inc, g, w_plus, w_minus, eps, damp, upd, e0, gtab, sm);
+}
+
+// The same for a class of a disjoint union of graphs: item e belongs to
+// instance inst[e], whose control block ctl[4*inst[e] ..] gates it (gated != 0).
+__global__ void __launch_bounds__(256) k_bdcm_edge_batch(const double* __restrict__ chi,
+                                                        const int32_t* __restrict__ rows,
+                                                        const int32_t* __restrict__ inc,
+                                                        const int32_t* __restrict__ inst, Geo g, double w_plus,
+                                                        double w_minus, double eps, double damp,
+                                                        double* __restrict__ upd, int64_t e0,
+                                                        double* __restrict__ gtab, const long long* __restrict__ ctl,
+                                                        int gated, const double* __restrict__ w_dev) {
+    if (gated && ctl[4 * (int64_t)inst[e0 + blockIdx.x] + 1]) return;      // the whole workgroup: one item
+    if (w_dev) {
+        w_plus = w_dev[0];
+        w_minus = w_dev[1];
+    }
+    extern __shared__ __align__(16) double sm[];
+    edge_item(chi, rows, inc, g, w_plus, w_minus, eps, damp, upd, e0, gtab, sm);
+}
+
 // scatter the class's new rows into chi; max |new - old| as double bits
 __global__ void __launch_bounds__(256) k_bdcm_commit(double* __restrict__ chi, const int32_t* __restrict__ rows,
                                                      int64_t m, int NC, const double* __restrict__ upd,
@@ -324,22 +352,80 @@ __global__ void __launch_bounds__(256) k_bdcm_commit(double* __restrict__ chi, c
     }
 }
 
+// The commit of a union class.  A stopped instance's rows stay as they are
+// (its upd rows were not written).  The maximum is reduced per row -- over
+// the min(NC, 64) lanes that hold one row's columns: NC is a power of 4 and a
+// wave's 64 consecutive elements start at a multiple of 64, so those lane
+// groups are aligned and an xor butterfly below the group size stays inside
+// one -- and goes by atomic max into the row's own instance.
+__global__ void __launch_bounds__(256) k_bdcm_commit_batch(double* __restrict__ chi, const int32_t* __restrict__ rows,
+                                                           const int32_t* __restrict__ inst, int64_t m, int NC,
+                                                           const double* __restrict__ upd,
+                                                           long long* __restrict__ ctl, int gated, int with_delta) {
+    const int64_t total = m * NC;
+    const int grp = NC < 64 ? NC : 64;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < total; base += (int64_t)gridDim.x * 256) {
+        const int64_t q = base + threadIdx.x;          // every lane of a wave shares the trip count
+        unsigned long long mx = 0;
+        int64_t gi = -1;
+        if (q < total) {
+            const int64_t e = q / NC;
+            const int col = (int)(q % NC);
+            gi = inst ? inst[e] : 0;
+            if (!(gated && ctl[4 * gi + 1])) {
+                double* p = chi + (int64_t)rows[e] * NC + col;
+                const double nv = upd[q];
+                mx = (unsigned long long)__double_as_longlong(fabs(nv - *p));
+                *p = nv;
+            }
+        }
+        if (with_delta) {
+            for (int off = grp >> 1; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_xor(mx, off, 64);
+                mx = o > mx ? o : mx;
+            }
+            if ((threadIdx.x & (grp - 1)) == 0 && mx)
+                atomicMax(reinterpret_cast<unsigned long long*>(ctl + 4 * gi), mx);
+        }
+    }
+}
+
 // the notebook's convergence loop on the device (nb:422-431):
 //   while delta > eps: delta = BDCM sweep; t += 1; if t >= T_max: stop
 // ctl[0] = delta bits of the running sweep, ctl[1] = stop flag, ctl[2] = t,
 // ctl[3] = delta bits of the last completed sweep.  One thread, plain stores.
-__global__ void k_bdcm_iter_begin(long long* __restrict__ ctl) {
-    if (threadIdx.x == 0 && ctl[1] == 0) ctl[0] = 0;
+__device__ inline void iter_begin(long long* ctl) {
+    if (ctl[1] == 0) ctl[0] = 0;
 }
 
-__global__ void k_bdcm_iter_end(long long* __restrict__ ctl, double eps, long long t_max) {
-    if (threadIdx.x != 0 || ctl[1] != 0) return;
+__device__ inline void iter_end(long long* ctl, double eps, long long t_max) {
+    if (ctl[1] != 0) return;
     const long long bits = ctl[0];
     const double delta = __longlong_as_double(bits);
     const long long t = ctl[2] + 1;
     ctl[2] = t;
     ctl[3] = bits;
     if (!(delta > eps) || t >= t_max) ctl[1] = 1;      // NaN ends the loop too (while NaN > eps is false)
+}
+
+__global__ void k_bdcm_iter_begin(long long* __restrict__ ctl) {
+    if (threadIdx.x == 0) iter_begin(ctl);
+}
+
+__global__ void k_bdcm_iter_end(long long* __restrict__ ctl, double eps, long long t_max) {
+    if (threadIdx.x == 0) iter_end(ctl, eps, t_max);
+}
+
+// the same rule for the control blocks ctl[G][4] of a batch, one thread per instance
+__global__ void __launch_bounds__(256) k_bdcm_iter_begin_batch(long long* __restrict__ ctl, int64_t G) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < G) iter_begin(ctl + 4 * g);
+}
+
+__global__ void __launch_bounds__(256) k_bdcm_iter_end_batch(long long* __restrict__ ctl, int64_t G, double eps,
+                                                             long long t_max) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < G) iter_end(ctl + 4 * g, eps, t_max);
 }
 
 // Zi_ER for one node-degree class (nb:211-276): zi[node] = max(sum_xa w Ai LL, eps)
@@ -365,17 +451,14 @@ __global__ void __launch_bounds__(256) k_bdcm_node(const double* __restrict__ ch
     if (lane == 0) zi[nodes[e]] = (z < eps) ? eps : z;
 }
 
-// Zij (nb:200-209) and the per-edge m_init term (nb:379-392)
-__global__ void __launch_bounds__(256) k_bdcm_edge_obs(const double* __restrict__ chi, const int32_t* __restrict__ edges,
-                                                       const int32_t* __restrict__ deg, int64_t E, int T, int ab,
-                                                       double eps, double* __restrict__ zij,
-                                                       double* __restrict__ mterm) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= E) return;
-    const int X = 1 << T, NC = X * X, XV = X / 2;
+// Zij (nb:200-209) and the per-edge m_init term (nb:379-392) of edge e, whose
+// messages u -> v and v -> u are the rows f and b
+__device__ inline void edge_obs_item(const double* __restrict__ f, const double* __restrict__ b,
+                                     const int32_t* __restrict__ edges, const int32_t* __restrict__ deg, int64_t e,
+                                     int T, int ab, double eps, double* __restrict__ zij,
+                                     double* __restrict__ mterm) {
+    const int X = 1 << T, XV = X / 2;
     const double du = (double)deg[edges[2 * e]], dv = (double)deg[edges[2 * e + 1]];
-    const double* f = chi + e * NC;
-    const double* b = chi + (e + E) * NC;
     double z = 0.0, mt = 0.0;
     for (int a = XV - 1; a >= 0; --a) {
         const int xa = 2 * a + ab;
@@ -390,6 +473,31 @@ __global__ void __launch_bounds__(256) k_bdcm_edge_obs(const double* __restrict_
     z = (z < eps) ? eps : z;
     zij[e] = z;
     if (mterm) mterm[e] = mt / z;
+}
+
+__global__ void __launch_bounds__(256) k_bdcm_edge_obs(const double* __restrict__ chi, const int32_t* __restrict__ edges,
+                                                       const int32_t* __restrict__ deg, int64_t E, int T, int ab,
+                                                       double eps, double* __restrict__ zij,
+                                                       double* __restrict__ mterm) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int NC = 1 << (2 * T);
+    edge_obs_item(chi + e * NC, chi + (e + E) * NC, edges, deg, e, T, ab, eps, zij, mterm);
+}
+
+// the same with the two rows of every edge given explicitly (a union of graphs:
+// the reverse of a forward row is not "row + E")
+__global__ void __launch_bounds__(256) k_bdcm_edge_obs_batch(const double* __restrict__ chi,
+                                                            const int32_t* __restrict__ fwd_row,
+                                                            const int32_t* __restrict__ rev_row,
+                                                            const int32_t* __restrict__ edges,
+                                                            const int32_t* __restrict__ deg, int64_t E, int T, int ab,
+                                                            double eps, double* __restrict__ zij,
+                                                            double* __restrict__ mterm) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int NC = 1 << (2 * T);
+    edge_obs_item(chi + (int64_t)fwd_row[e] * NC, chi + (int64_t)rev_row[e] * NC, edges, deg, e, T, ab, eps, zij, mterm);
 }
 
 // deterministic two-level sum (of logs): fixed grid, fixed tree
@@ -421,6 +529,33 @@ __global__ void __launch_bounds__(256) k_sum_final(const double* __restrict__ pa
     for (int i = threadIdx.x; i < np; i += 256) s += part[i];
     const double t = block_sum256(s, red);
     if (threadIdx.x == 0) out[0] = t;
+}
+
+// per segment what k_sum_partial / k_sum_final do for one array: block
+// (b, g) = blockIdx.x of a kSumBlocks x G grid is block b of k_sum_partial on
+// x[seg_ptr[g] : seg_ptr[g+1]], then the same final tree per segment
+__global__ void __launch_bounds__(256) k_segsum_partial(const double* __restrict__ x,
+                                                        const int64_t* __restrict__ seg_ptr, int take_log,
+                                                        double* __restrict__ part) {
+    __shared__ double red[256];
+    const int64_t g = blockIdx.x / kSumBlocks;
+    const int b = blockIdx.x % kSumBlocks;
+    const int64_t lo = seg_ptr[g], n = seg_ptr[g + 1] - lo;
+    const double* xs = x + lo;
+    double s = 0.0;
+    for (int64_t i = (int64_t)b * 256 + threadIdx.x; i < n; i += (int64_t)kSumBlocks * 256)
+        s += take_log ? log(xs[i]) : xs[i];
+    const double t = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+__global__ void __launch_bounds__(256) k_segsum_final(const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double red[256];
+    const double* ps = part + (int64_t)blockIdx.x * kSumBlocks;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < kSumBlocks; i += 256) s += ps[i];
+    const double t = block_sum256(s, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 template <typename K>
@@ -555,5 +690,79 @@ extern "C" int mjx_sum_f64(const double* x, int64_t n, int take_log, double* wor
     MJX_LAUNCH_CHECK("k_sum_partial");
     k_sum_final<<<1, 256, 0, st>>>(work, kSumBlocks, out);
     MJX_LAUNCH_CHECK("k_sum_final");
+    return MJX_OK;
+}
+
+/* ---- a batch of graphs as one disjoint union ---- */
+
+extern "C" int mjx_bdcm_update_class_batch(double* chi, const int32_t* rows, const int32_t* inc, const int32_t* inst,
+                                           int64_t m, int D, int p, int c, int attr_value, double lmbd, double damp,
+                                           double eps, double* upd, long long* ctl, int flags, const double* w_dev,
+                                           void* scratch, int64_t scratch_bytes, void* stream) {
+    if (m < 0 || !chi || (flags & ~(MJX_BDCM_GATE | MJX_BDCM_DELTA))) return MJX_EINVAL;
+    if (flags && (!inst || !ctl)) return MJX_EINVAL;
+    if (m == 0) return MJX_OK;
+    if (!rows || !upd || (D > 0 && !inc) || !(damp > 0.0)) return MJX_EINVAL;
+    Geo g;
+    if (!make_geo(D, p, c, attr_value, &g)) return MJX_ERANGE;
+    size_t lds;
+    bool in_lds;
+    const int64_t per = plan_launch(g, m, scratch, scratch_bytes, &lds, &in_lds);
+    if (per < 1) return MJX_ERANGE;
+    hipStream_t st = as_stream(stream);
+    int rc = set_lds(k_bdcm_edge_batch);
+    if (rc) return rc;
+    const int gated = (flags & MJX_BDCM_GATE) ? 1 : 0;
+    for (int64_t e0 = 0; e0 < m; e0 += per) {
+        const int64_t cnt = (m - e0 < per) ? m - e0 : per;
+        if (cnt > (int64_t)INT32_MAX) return MJX_ERANGE;
+        k_bdcm_edge_batch<<<(unsigned)cnt, item_threads(g), lds, st>>>(chi, rows, inc, inst, g, exp(-lmbd), exp(lmbd), eps,
+                                                                        damp, upd, e0, in_lds ? nullptr : (double*)scratch,
+                                                                        ctl, gated, w_dev);
+        MJX_LAUNCH_CHECK("k_bdcm_edge_batch");
+    }
+    const int NC = g.X * g.X;
+    k_bdcm_commit_batch<<<grid_for(m * NC), 256, 0, st>>>(chi, rows, inst, m, NC, upd, ctl, gated,
+                                                          (flags & MJX_BDCM_DELTA) ? 1 : 0);
+    MJX_LAUNCH_CHECK("k_bdcm_commit_batch");
+    return MJX_OK;
+}
+
+extern "C" int mjx_bdcm_iter_begin_batch(long long* ctl, int64_t G, void* stream) {
+    if (!ctl || G < 1 || G > (int64_t)INT32_MAX) return MJX_EINVAL;
+    k_bdcm_iter_begin_batch<<<(unsigned)((G + 255) / 256), 256, 0, as_stream(stream)>>>(ctl, G);
+    MJX_LAUNCH_CHECK("k_bdcm_iter_begin_batch");
+    return MJX_OK;
+}
+
+extern "C" int mjx_bdcm_iter_end_batch(long long* ctl, int64_t G, double eps, int64_t t_max, void* stream) {
+    if (!ctl || G < 1 || G > (int64_t)INT32_MAX) return MJX_EINVAL;
+    k_bdcm_iter_end_batch<<<(unsigned)((G + 255) / 256), 256, 0, as_stream(stream)>>>(ctl, G, eps, (long long)t_max);
+    MJX_LAUNCH_CHECK("k_bdcm_iter_end_batch");
+    return MJX_OK;
+}
+
+extern "C" int mjx_bdcm_edge_obs_batch(const double* chi, const int32_t* fwd_row, const int32_t* rev_row,
+                                       const int32_t* edges, const int32_t* deg, int64_t E_total, int p, int c,
+                                       int attr_value, double eps, double* zij, double* m_term, void* stream) {
+    if (E_total < 0 || p < 0 || c < 1 || p + c > kMaxT || (attr_value != 1 && attr_value != -1)) return MJX_EINVAL;
+    if (E_total == 0) return MJX_OK;
+    if (!chi || !fwd_row || !rev_row || !edges || !deg || !zij) return MJX_EINVAL;
+    k_bdcm_edge_obs_batch<<<(unsigned)((E_total + 255) / 256), 256, 0, as_stream(stream)>>>(
+        chi, fwd_row, rev_row, edges, deg, E_total, p + c, attr_value > 0 ? 1 : 0, eps, zij, m_term);
+    MJX_LAUNCH_CHECK("k_bdcm_edge_obs_batch");
+    return MJX_OK;
+}
+
+extern "C" int mjx_segsum_f64(const double* x, const int64_t* seg_ptr, int64_t G, int take_log, double* work,
+                              double* out, void* stream) {
+    if (G < 0 || G > (int64_t)INT32_MAX / kSumBlocks) return MJX_EINVAL;
+    if (G == 0) return MJX_OK;
+    if (!x || !seg_ptr || !work || !out) return MJX_EINVAL;
+    hipStream_t st = as_stream(stream);
+    k_segsum_partial<<<(unsigned)(G * kSumBlocks), 256, 0, st>>>(x, seg_ptr, take_log, work);
+    MJX_LAUNCH_CHECK("k_segsum_partial");
+    k_segsum_final<<<(unsigned)G, 256, 0, st>>>(work, out);
+    MJX_LAUNCH_CHECK("k_segsum_final");
     return MJX_OK;
 }
