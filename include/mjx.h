@@ -144,6 +144,54 @@ int mjx_popcount_np(const uint64_t* bits, int64_t n, unsigned long long* counts,
 int mjx_popcount_rp(const uint64_t* bits, int64_t n, int64_t words,
                     unsigned long long* counts, void* stream);
 
+/* ---- run to the attractor (no reference counterpart) -------------------- */
+/*
+ * Synchronous majority dynamics with always-stay ties on an undirected graph
+ * end in a fixed point or a 2-cycle (Goles & Olivos).  Definitions, for one
+ * replica:
+ *   trajectory  s(0) = s0, s(t+1) = onestep_majority(s(t));
+ *   p = min{ t >= 0 : s(t+2) = s(t) }   (once it holds it holds for all later t);
+ *   c = 1 if s(p+1) = s(p), else c = 2;
+ *   with a sweep budget t_max a replica with p > t_max reports p = -1, c = 0;
+ *   sum_att[r] = (sum s(p), sum s(p+1)): equal when c = 1; consensus means
+ *   both equal n.
+ *
+ * mjx_sweep_track_ell_rp / mjx_sweep_track_csr_rp: one step of
+ * mjx_rollout_ell_rp / mjx_rollout_csr_rp_ordered (s_out = onestep(s_in);
+ * counts nullable, [64*words] added) plus tracking.  diff: uint64[2*words],
+ * ORed into (caller zeroes it): bit r&63 of diff[r>>6] is set iff some node of
+ * replica r has s_out != s_in; bit r&63 of diff[words + (r>>6)] iff some node
+ * has s_out != s_prev.  s_prev is nullable: that half is then untouched.
+ * s_out may be the same buffer as s_prev (the ping-pong case: every word is
+ * read and then written by the one thread that owns it); s_out may not alias
+ * s_in, nor s_prev s_in.  Padding replicas (bits 0 in every state, as
+ * mjx_pack_rp and mjx_random_spins_rp write them) never set a flag.
+ * Out of scope: the degree-class ELL layout, the node-packed layout and a
+ * graph per replica (rep_graph).
+ */
+int mjx_sweep_track_ell_rp(const int32_t* adj, int64_t n, int d, int64_t words,
+                           const uint64_t* s_in, const uint64_t* s_prev, uint64_t* s_out,
+                           unsigned long long* counts, uint64_t* diff, void* stream);
+int mjx_sweep_track_csr_rp(const int64_t* row_ptr, const int32_t* col, const int32_t* order, int64_t n,
+                           int64_t words, const uint64_t* s_in, const uint64_t* s_prev, uint64_t* s_out,
+                           unsigned long long* counts, uint64_t* diff, void* stream);
+/* Bookkeeping after tracked sweep k >= 2 (which wrote s(k)): diff = that
+ * sweep's flags, diff_prev = those of sweep k-1 (its first half is read),
+ * cnt_km2 / cnt_km1 = the +1 counts of s(k-2) / s(k-1).  Every replica r < R
+ * with p[r] == -1 whose "s(k) != s(k-2)" bit is clear gets p[r] = k-2, c[r] =
+ * 2 if its "s(k-1) != s(k-2)" bit is set else 1, sum_att[2r], sum_att[2r+1] =
+ * 2*cnt - n of s(k-2), s(k-1); *unsettled drops by the number settled.  The
+ * caller starts with p = -1, c = 0, *unsettled = R. */
+int mjx_attractor_record(int64_t n, int64_t R, int k, const uint64_t* diff, const uint64_t* diff_prev,
+                         const unsigned long long* cnt_km2, const unsigned long long* cnt_km1,
+                         int32_t* p, int32_t* c, int64_t* sum_att, unsigned long long* unsettled, void* stream);
+/* Random starts, replica-packed bits[n*ceil(R/64)]: bit (v, r) is 1 iff
+ * x < floor(prob[r] * 2^32) compared in 64 bits (prob: device double[R] in
+ * [0, 1]; 1 gives all +1, 0 all -1), x = word r&3 of philox4x32_10(counter =
+ * (v_lo, v_hi, r>>2, 0), key = (seed_lo, seed_hi)): a pure function of
+ * (seed, v, r), whatever R is.  Padding replicas are 0. */
+int mjx_random_spins_rp(int64_t n, int64_t R, uint64_t seed, const double* prob, uint64_t* bits, void* stream);
+
 /* ---- simulated annealing (code/SA_RRG.py:44-92), R = 64*W replicas ------ */
 /*
  * Per-replica state, all device arrays of length R unless noted.  Replica r

@@ -39,6 +39,10 @@ SIGNATURES = {
     "mjx_gather_floor_class": [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_vp],
     "mjx_popcount_np": [c_vp, c_i64, c_vp, c_vp],
     "mjx_popcount_rp": [c_vp, c_i64, c_i64, c_vp, c_vp],
+    "mjx_sweep_track_ell_rp": [c_vp, c_i64, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_sweep_track_csr_rp": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_attractor_record": [c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_random_spins_rp": [c_i64, c_i64, c_u64, c_vp, c_vp, c_vp],
     "mjx_sa_init": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_vp, c_dbl, c_dbl,
                     c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_sa_init_mt": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_dbl, c_dbl,

@@ -14,6 +14,10 @@ and write its np.savez keys.
   bdcm  code/ER_BDCM_entropy.ipynb raw lines 456-481 (n, deg, num_rep, p, c,
         eps, damppar, attr_value, epsilon, T_max, a, dl), output :515
         ("ER_p{p}.npz": m_init, ent1, ent, ... T_max, num_rep)
+  attractor  no reference script: the random-initialisation baseline
+        (attractor.consensus_curve) on one random regular or Erdos-Renyi
+        graph; output "attractor_{graph}.npz": m_init, consensus, c1, c2,
+        unsettled, p, c, sum_att, init_plus
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -120,6 +124,16 @@ def build_parser():
     bd.add_argument("--batch", type=int, default=0,
                     help="run that many graphs at a time as one union graph (0: one after the other); same output")
     _common(bd)
+    at = sub.add_parser("attractor", help="random starts run to their attractors (no reference script)")
+    at.add_argument("--graph", choices=("rrg", "er"), default="rrg")
+    at.add_argument("--n", type=int, default=10000)
+    at.add_argument("--d", type=int, default=4, help="degree (rrg)")
+    at.add_argument("--deg", type=float, default=2.0, help="mean degree (er; prob = deg/(n-1))")
+    at.add_argument("--m-init", type=float, nargs="+", default=[0.0], help="initial magnetisations")
+    at.add_argument("--t-max", type=int, default=4096, help="sweep budget: p > t_max is reported as -1")
+    at.add_argument("--chunk", type=int, default=16, help="sweeps between two host reads of the unsettled counter")
+    at.add_argument("--batch", type=int, default=None, help="m_inits per replica-packed batch (default: all)")
+    _common(at)
     return ap
 
 
@@ -246,9 +260,29 @@ def run_bdcm(a):
     return res
 
 
+def run_attractor(a):
+    from .attractor import consensus_curve
+    from .graph import Graph, erdos_renyi, random_regular_graph
+    R = a.replicas if a.replicas is not None else 64
+    gs = a.graph_seed if a.graph_seed is not None else a.seed
+    _devices(a.gpus)                        # one graph shared by every replica: the current device
+    t0 = time.time()
+    if a.graph == "rrg":
+        g = random_regular_graph(a.d, a.n, seed=gs)
+    else:
+        g = Graph.csr(*erdos_renyi(a.n, a.deg / (a.n - 1), seed=gs))
+    res = consensus_curve(g, a.m_init, R, a.seed, t_max=a.t_max, chunk=a.chunk, batch=a.batch)
+    out = a.out or f"attractor_{a.graph}.npz"
+    np.savez(out, **res)
+    print(f"attractor: {a.graph} n={a.n}, m_init {list(a.m_init)} x {R} replicas, consensus "
+          f"{res['consensus'].tolist()}, c=1 {res['c1'].tolist()}, c=2 {res['c2'].tolist()}, unsettled "
+          f"{res['unsettled'].tolist()}, max p {int(res['p'].max())}, {time.time() - t0:.1f} s -> {out}", flush=True)
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm}[a.cmd](a)
+    return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm, "attractor": run_attractor}[a.cmd](a)
 
 
 if __name__ == "__main__":

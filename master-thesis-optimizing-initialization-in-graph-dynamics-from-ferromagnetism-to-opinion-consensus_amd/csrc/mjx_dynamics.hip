@@ -10,6 +10,7 @@
 // HBM-bound by design: per node and sweep the kernels read d int32 indices,
 // gather d neighbour state rows, read the node's own row and write one row.
 #include "mjx_common.h"
+#include "mjx_philox.h"
 #include <algorithm>
 #include <string.h>
 #include <stdio.h>
@@ -620,6 +621,273 @@ __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restri
         }
     }
     count_epilogue<VW, COUNT, kBlock, 10>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
+}
+
+// ---------------------------------------------------------------------------
+// Tracked replica-packed sweeps (run to the attractor, include/mjx.h): one
+// step of the sweeps above that also reports, per replica, whether any node
+// changed against s_in ("s(t+1) != s(t)": the own word is already in
+// registers) and against s_prev ("s(t+1) != s(t-1)": one more streamed word
+// per node, the very word a ping-pong sweep overwrites -- s_out may be
+// s_prev; the thread that owns (node, unit) loads it before it stores).
+// A thread's replica range is fixed, so it ORs out ^ own and out ^ prev into
+// 2*VW registers over its nodes; the block ORs them in LDS and issues one
+// global atomicOr per non-zero flag word.  Sibling kernels: the sweeps above
+// are not touched, so the untracked rollouts compile to the code they had.
+// Dynamic LDS: the fused counters (Us*VW*64 unsigned, when use_lds), then
+// 2*Us*VW flag words (when use_dlds; else Us >= block size, every thread of a
+// block owns another unit and ORs its words into `diff` itself).
+// ---------------------------------------------------------------------------
+template <int VW>
+struct DiffAcc {
+    u64 in[VW], prev[VW];      // ORs of out ^ own and of out ^ prev
+    __device__ __forceinline__ void reset() {
+#pragma unroll
+        for (int q = 0; q < VW; ++q) in[q] = prev[q] = 0;
+    }
+    __device__ __forceinline__ void add(const u64* out, const u64* own) {
+#pragma unroll
+        for (int q = 0; q < VW; ++q) in[q] |= out[q] ^ own[q];
+    }
+    __device__ __forceinline__ void add_prev(const u64* out, const u64* pv) {
+#pragma unroll
+        for (int q = 0; q < VW; ++q) prev[q] |= out[q] ^ pv[q];
+    }
+};
+
+__device__ __forceinline__ u64* diff_lds(unsigned* lds, int use_lds, int64_t Us, int VW) {
+    return reinterpret_cast<u64*>(lds + (use_lds ? Us * VW * 64 : 0));   // 8-byte aligned: VW*64 unsigneds a unit
+}
+
+template <int VW>
+__device__ __forceinline__ void diff_init(u64* dl, int64_t Us, int use_dlds) {
+    if (use_dlds) {
+        for (int64_t i = threadIdx.x; i < 2 * Us * VW; i += kBlock) dl[i] = 0;
+        __syncthreads();
+    }
+}
+
+// diff[0 .. W): changed against s_in; diff[W .. 2W): against s_prev (has_prev)
+template <int VW, typename DST>
+__device__ __forceinline__ void diff_or(const DiffAcc<VW>& da, bool has_prev, DST* first, DST* second) {
+#pragma unroll
+    for (int q = 0; q < VW; ++q)
+        if (da.in[q]) atomicOr(&first[q], da.in[q]);
+    if (has_prev) {
+#pragma unroll
+        for (int q = 0; q < VW; ++q)
+            if (da.prev[q]) atomicOr(&second[q], da.prev[q]);
+    }
+}
+
+template <int VW>
+__device__ __forceinline__ void diff_epilogue(const DiffAcc<VW>& da, bool active, bool has_prev, int64_t unit,
+                                              int64_t unit0, int64_t Us, int64_t W, u64* dl, int use_dlds,
+                                              u64* __restrict__ diff) {
+    if (use_dlds) {
+        if (active) diff_or<VW>(da, has_prev, dl + (unit - unit0) * VW, dl + (Us + unit - unit0) * VW);
+        __syncthreads();  // every thread of the block reaches this (no early return)
+        const int64_t tot = (has_prev ? 2 : 1) * Us * VW;
+        for (int64_t i = threadIdx.x; i < tot; i += kBlock) {
+            const u64 x = dl[i];
+            if (x) {
+                const int64_t h = i / (Us * VW), w = i - h * (Us * VW);
+                atomicOr(&diff[h * W + unit0 * VW + w], x);
+            }
+        }
+    } else if (active) {
+        diff_or<VW>(da, has_prev, diff + unit * VW, diff + W + unit * VW);
+    }
+}
+
+template <int D, int VW, bool COUNT>
+__global__ void __launch_bounds__(kBlock) k_sweep_track_ell_rp(const int32_t* __restrict__ adj, int64_t n, int64_t W,
+                                                               const u64* __restrict__ s_in, const u64* s_prev,
+                                                               u64* s_out, unsigned long long* __restrict__ counts,
+                                                               int use_lds, u64* __restrict__ diff, int use_dlds,
+                                                               int64_t unit0, int64_t Us) {
+    extern __shared__ unsigned lds_cnt[];
+    u64* const dl = diff_lds(lds_cnt, COUNT ? use_lds : 0, Us, VW);
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
+    const int64_t unit = unit0 + t % Us, slot = t / Us;
+    const bool active = slot < slots, has_prev = s_prev != nullptr;
+    VertCounter<VW> vc;
+    DiffAcc<VW> da;
+    da.reset();
+    if constexpr (COUNT) {
+        vc.reset();
+        lds_count_init<VW>(lds_cnt, Us, use_lds);
+    }
+    diff_init<VW>(dl, Us, use_dlds);
+    if (active) {
+        for (int64_t v = slot; v < n; v += slots) {
+            int32_t k[D];
+            load_adj<D>(adj, v, k);
+            u64 x[D][VW], own[VW], prev[VW], out[VW];
+#pragma unroll
+            for (int j = 0; j < D; ++j) ldv<VW>(s_in + (int64_t)k[j] * W + unit * VW, x[j]);
+            ldv<VW>(s_in + v * W + unit * VW, own);
+            if (has_prev) ldv<VW>(s_prev + v * W + unit * VW, prev);
+#pragma unroll
+            for (int q = 0; q < VW; ++q) {
+                u64 xs[D];
+#pragma unroll
+                for (int j = 0; j < D; ++j) xs[j] = x[j][q];
+                out[q] = majority_fixed<D>(xs, own[q]);
+            }
+            stv<VW>(s_out + v * W + unit * VW, out);
+            da.add(out, own);
+            if (has_prev) da.add_prev(out, prev);
+            if constexpr (COUNT) {
+                vc.add(out);
+                if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
+            }
+        }
+    }
+    count_epilogue<VW, COUNT>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
+    diff_epilogue<VW>(da, active, has_prev, unit, unit0, Us, W, dl, use_dlds, diff);
+}
+
+// the new bits of this thread's unit of node v, rows of runtime length
+// (ELL rows of length d, or CSR rows): the node body of k_sweep_gen_rp
+template <int VW, bool CSR>
+__device__ __forceinline__ void gen_node(const int32_t* __restrict__ adj, int d, const int64_t* __restrict__ row_ptr,
+                                         const int32_t* __restrict__ col, int64_t v, int64_t W,
+                                         const u64* __restrict__ s_in, int64_t unit, u64* own, u64* out) {
+    int64_t b, e;
+    const int32_t* nbr;
+    if constexpr (CSR) {
+        b = row_ptr[v]; e = row_ptr[v + 1]; nbr = col;
+    } else {
+        b = v * d; e = b + d; nbr = adj;
+    }
+    const int deg = (int)(e - b);
+    BitCounter<8> bc[VW];
+#pragma unroll
+    for (int q = 0; q < VW; ++q) bc[q].reset();
+    int64_t j = b;
+    for (; j + 4 <= e; j += 4) {
+        int32_t k[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) k[m] = nbr[j + m];
+        u64 x[4][VW];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
+    }
+    for (; j < e; ++j) {
+        u64 x[VW];
+        ldv<VW>(s_in + (int64_t)nbr[j] * W + unit * VW, x);
+#pragma unroll
+        for (int q = 0; q < VW; ++q) bc[q].add(x[q]);
+    }
+    ldv<VW>(s_in + v * W + unit * VW, own);
+#pragma unroll
+    for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(deg, own[q]);
+}
+
+template <int VW, bool COUNT, bool CSR>
+__global__ void __launch_bounds__(kBlock) k_sweep_track_gen_rp(const int32_t* __restrict__ adj, int d,
+                                                               const int64_t* __restrict__ row_ptr,
+                                                               const int32_t* __restrict__ col,
+                                                               const int32_t* __restrict__ order, int64_t n,
+                                                               int64_t W, const u64* __restrict__ s_in,
+                                                               const u64* s_prev, u64* s_out,
+                                                               unsigned long long* __restrict__ counts, int use_lds,
+                                                               u64* __restrict__ diff, int use_dlds, int64_t unit0,
+                                                               int64_t Us) {
+    extern __shared__ unsigned lds_cnt[];
+    u64* const dl = diff_lds(lds_cnt, COUNT ? use_lds : 0, Us, VW);
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
+    const int64_t unit = unit0 + t % Us, slot = t / Us;
+    const bool active = slot < slots, has_prev = s_prev != nullptr;
+    VertCounter<VW, 10> vc;
+    DiffAcc<VW> da;
+    da.reset();
+    if constexpr (COUNT) {
+        vc.reset();
+        lds_count_init<VW>(lds_cnt, Us, use_lds);
+    }
+    diff_init<VW>(dl, Us, use_dlds);
+    if (active) {
+        for (int64_t i = slot; i < n; i += slots) {
+            const int64_t v = order ? (int64_t)order[i] : i;
+            u64 own[VW], prev[VW], out[VW];
+            if (has_prev) ldv<VW>(s_prev + v * W + unit * VW, prev);
+            gen_node<VW, CSR>(adj, d, row_ptr, col, v, W, s_in, unit, own, out);
+            stv<VW>(s_out + v * W + unit * VW, out);
+            da.add(out, own);
+            if (has_prev) da.add_prev(out, prev);
+            if constexpr (COUNT) {
+                vc.add(out);
+                if (vc.added == (1 << decltype(vc)::KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
+            }
+        }
+    }
+    count_epilogue<VW, COUNT, kBlock, 10>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
+    diff_epilogue<VW>(da, active, has_prev, unit, unit0, Us, W, dl, use_dlds, diff);
+}
+
+// Attractor bookkeeping after sweep k >= 2 (one thread a replica): a replica
+// still without p whose s(k) == s(k-2) settles with p = k-2, c from the
+// previous sweep's "s(k-1) != s(k-2)" bit, sum_att from the +1 counts of
+// s(k-2) and s(k-1); `unsettled` drops by the number settled (one atomic a wave).
+__global__ void __launch_bounds__(kBlock) k_attractor_record(int64_t n, int64_t R, int64_t W, int k,
+                                                             const u64* __restrict__ diff,
+                                                             const u64* __restrict__ diff_prev,
+                                                             const unsigned long long* __restrict__ cnt_km2,
+                                                             const unsigned long long* __restrict__ cnt_km1,
+                                                             int32_t* __restrict__ p, int32_t* __restrict__ c,
+                                                             int64_t* __restrict__ sum_att,
+                                                             unsigned long long* __restrict__ unsettled) {
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool settle = false;
+    if (r < R && p[r] < 0) {
+        const int64_t w = r >> 6;
+        const int b = (int)(r & 63);
+        settle = ((diff[W + w] >> b) & 1ull) == 0;
+        if (settle) {
+            p[r] = k - 2;
+            c[r] = ((diff_prev[w] >> b) & 1ull) ? 2 : 1;
+            sum_att[2 * r] = 2 * (int64_t)cnt_km2[r] - n;
+            sum_att[2 * r + 1] = 2 * (int64_t)cnt_km1[r] - n;
+        }
+    }
+    const u64 m = __ballot(settle);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(unsettled, 0ull - (unsigned long long)__popcll(m));
+}
+
+// Random starts: word (v, w) of the replica-packed state; spin (v, r) is +1 iff
+// x < floor(prob[r] * 2^32), x = word r & 3 of philox4x32_10(counter (v lo,
+// v hi, r >> 2, 0), key = seed) -- a pure function of (seed, v, r).
+__global__ void __launch_bounds__(kBlock) k_random_spins_rp(int64_t n, int64_t R, int64_t W, uint64_t seed,
+                                                            const double* __restrict__ prob, u64* __restrict__ bits) {
+    const int64_t total = n * W;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (int64_t)gridDim.x * kBlock) {
+        const int64_t v = t / W, w = t - v * W;
+        u64 word = 0;
+        for (int g = 0; g < 16; ++g) {
+            const int64_t r0 = w * 64 + 4 * g;
+            if (r0 >= R) break;
+            uint32_t x[4];
+            philox4x32_10((uint32_t)v, (uint32_t)((uint64_t)v >> 32), (uint32_t)(r0 >> 2), 0u, k0, k1, x);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (r0 + j < R) {
+                    const double pr = fmin(fmax(prob[r0 + j], 0.0), 1.0);
+                    const u64 thr = (u64)floor(pr * 4294967296.0);          // 0 .. 2^32, compared in 64 bits
+                    if ((u64)x[j] < thr) word |= 1ull << (4 * g + j);
+                }
+            }
+        }
+        bits[t] = word;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1584,4 +1852,123 @@ extern "C" int mjx_rollout_csr_rp(const int64_t* row_ptr, const int32_t* col, in
                                   const uint64_t* s_in, uint64_t* s_out, uint64_t* tmp, int steps,
                                   unsigned long long* counts, void* stream) {
     return mjx_rollout_csr_rp_ordered(row_ptr, col, nullptr, n, words, s_in, s_out, tmp, steps, counts, stream);
+}
+
+// ---- run to the attractor: tracked sweeps, bookkeeping, random starts -------
+
+constexpr int64_t kMaxLdsDiffWords = 1024;   // 2 x 8 KiB of LDS flag words per block
+
+// Geometry of a tracked launch over all U units: the fused counters' LDS as in
+// rp_geometry, then the flag words.  Above kMaxLdsDiffWords words U >= 512 >
+// the block size, so the threads of a block own distinct units.
+static int track_geometry(int64_t n, int64_t W, bool counting, int* vw, int* use_lds, int* use_dlds, size_t* lds) {
+    int grid;
+    int rc = rp_geometry(n, W, units_of(W), &grid, vw, use_lds, lds);
+    if (rc) return rc;
+    if (!counting) { *lds = 0; *use_lds = 0; }
+    *use_dlds = (W <= kMaxLdsDiffWords) ? 1 : 0;
+    if (*use_dlds) *lds += (size_t)(2 * W * sizeof(u64));
+    return MJX_OK;
+}
+
+static int check_track_args(int64_t n, int64_t words, const void* s_in, const void* s_prev, const void* s_out,
+                            const void* diff) {
+    if (n < 0 || words < 1 || !diff || (n > 0 && (!s_in || !s_out))) return MJX_EINVAL;
+    if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
+    if (overlaps(s_in, s_out) || overlaps(s_in, s_prev)) return MJX_EINVAL;    // s_out == s_prev: the ping-pong case
+    return MJX_OK;
+}
+
+extern "C" int mjx_sweep_track_ell_rp(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
+                                      const uint64_t* s_prev, uint64_t* s_out, unsigned long long* counts,
+                                      uint64_t* diff, void* stream) {
+    int rc = check_track_args(n, words, s_in, s_prev, s_out, diff);
+    if (rc) return rc;
+    if (d < 0 || d > 255 || (n > 0 && d > 0 && !adj)) return MJX_EINVAL;
+    if (n == 0) return MJX_OK;
+    int vw, use_lds, use_dlds; size_t lds;
+    rc = track_geometry(n, words, counts != nullptr, &vw, &use_lds, &use_dlds, &lds);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    const int64_t U = units_of(words);
+    const u64* in = (const u64*)s_in;
+    const u64* prev = (const u64*)s_prev;
+    u64* out = (u64*)s_out;
+    u64* df = (u64*)diff;
+    auto ell = [&](auto kern) {
+        const int g = resident_grid(kern, kBlock, lds, n * U);
+        kern<<<g, kBlock, lds, st>>>(adj, n, words, in, prev, out, counts, use_lds, df, use_dlds, (int64_t)0, U);
+    };
+    auto gen = [&](auto kern) {
+        const int g = resident_grid(kern, kBlock, lds, n * U);
+        kern<<<g, kBlock, lds, st>>>(adj, d, nullptr, nullptr, nullptr, n, words, in, prev, out, counts, use_lds, df,
+                                     use_dlds, (int64_t)0, U);
+    };
+#define MJX_TRACK_ELL(VWV, C)                                             \
+    switch (d) {                                                          \
+        case 3: ell(k_sweep_track_ell_rp<3, VWV, C>); break;              \
+        case 4: ell(k_sweep_track_ell_rp<4, VWV, C>); break;              \
+        case 6: ell(k_sweep_track_ell_rp<6, VWV, C>); break;              \
+        default: gen(k_sweep_track_gen_rp<VWV, C, false>); break;         \
+    }
+    if (vw == 2) {
+        if (counts) { MJX_TRACK_ELL(2, true) } else { MJX_TRACK_ELL(2, false) }
+    } else {
+        if (counts) { MJX_TRACK_ELL(1, true) } else { MJX_TRACK_ELL(1, false) }
+    }
+#undef MJX_TRACK_ELL
+    MJX_LAUNCH_CHECK("mjx_sweep_track_ell_rp");
+    return MJX_OK;
+}
+
+extern "C" int mjx_sweep_track_csr_rp(const int64_t* row_ptr, const int32_t* col, const int32_t* order, int64_t n,
+                                      int64_t words, const uint64_t* s_in, const uint64_t* s_prev, uint64_t* s_out,
+                                      unsigned long long* counts, uint64_t* diff, void* stream) {
+    int rc = check_track_args(n, words, s_in, s_prev, s_out, diff);
+    if (rc) return rc;
+    if (n > 0 && !row_ptr) return MJX_EINVAL;
+    if (n == 0) return MJX_OK;
+    int vw, use_lds, use_dlds; size_t lds;
+    rc = track_geometry(n, words, counts != nullptr, &vw, &use_lds, &use_dlds, &lds);
+    if (rc) return rc;
+    hipStream_t st = as_stream(stream);
+    const int64_t U = units_of(words);
+    auto csr = [&](auto kern) {
+        const int g = resident_grid(kern, kBlock, lds, n * U);
+        kern<<<g, kBlock, lds, st>>>(nullptr, 0, row_ptr, col, order, n, words, (const u64*)s_in, (const u64*)s_prev,
+                                     (u64*)s_out, counts, use_lds, (u64*)diff, use_dlds, (int64_t)0, U);
+    };
+    if (vw == 2) {
+        if (counts) csr(k_sweep_track_gen_rp<2, true, true>); else csr(k_sweep_track_gen_rp<2, false, true>);
+    } else {
+        if (counts) csr(k_sweep_track_gen_rp<1, true, true>); else csr(k_sweep_track_gen_rp<1, false, true>);
+    }
+    MJX_LAUNCH_CHECK("mjx_sweep_track_csr_rp");
+    return MJX_OK;
+}
+
+extern "C" int mjx_attractor_record(int64_t n, int64_t R, int k, const uint64_t* diff, const uint64_t* diff_prev,
+                                    const unsigned long long* cnt_km2, const unsigned long long* cnt_km1,
+                                    int32_t* p, int32_t* c, int64_t* sum_att, unsigned long long* unsettled,
+                                    void* stream) {
+    if (n < 0 || R < 1 || k < 2 || !diff || !diff_prev || !cnt_km2 || !cnt_km1 || !p || !c || !sum_att || !unsettled)
+        return MJX_EINVAL;
+    const int64_t W = (R + 63) / 64;
+    const int64_t blocks = (W * 64 + kBlock - 1) / kBlock;
+    if (blocks > (int64_t)INT32_MAX) return MJX_ERANGE;
+    k_attractor_record<<<(unsigned)blocks, kBlock, 0, as_stream(stream)>>>(n, R, W, k, (const u64*)diff,
+                                                                           (const u64*)diff_prev, cnt_km2, cnt_km1, p,
+                                                                           c, sum_att, unsettled);
+    MJX_LAUNCH_CHECK("mjx_attractor_record");
+    return MJX_OK;
+}
+
+extern "C" int mjx_random_spins_rp(int64_t n, int64_t R, uint64_t seed, const double* prob, uint64_t* bits,
+                                   void* stream) {
+    if (n < 0 || R < 1 || !prob || (n > 0 && !bits)) return MJX_EINVAL;
+    if (n == 0) return MJX_OK;
+    const int64_t W = (R + 63) / 64;
+    k_random_spins_rp<<<grid_for(n * W), kBlock, 0, as_stream(stream)>>>(n, R, W, seed, prob, (u64*)bits);
+    MJX_LAUNCH_CHECK("mjx_random_spins_rp");
+    return MJX_OK;
 }

@@ -23,6 +23,7 @@
 #include <memory>
 #include <mutex>
 #include "mjx_sa_core.h"
+#include "mjx_philox.h"
 #include <math.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -827,23 +828,9 @@ __global__ void __launch_bounds__(64) k_sa_tape(int64_t n, int64_t R, int64_t K,
     if (lane == 0) st.mt_idx[r] = idx;
 }
 
-// Philox-4x32-10 (Salmon et al., SC'11; Random123's philox4x32_10): the
-// NON-parity proposal stream (mjx_sa_state.philox_key).  Ten
-// rounds of two 32x32->64 multiplies, the key bumped by the Weyl constants
-// between rounds; oracle/orc_majority.c's orc_philox4x32_10 is the checker.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&x)[4]) {
-#pragma unroll
-    for (int q = 0; q < 10; ++q) {
-        if (q > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
-
+// Philox-4x32-10 (mjx_philox.h): the NON-parity proposal stream
+// (mjx_sa_state.philox_key).
+//
 // the Philox tape: entry (k, r) = the proposal of step t_r + k of replica r
 // (counter (t lo, t hi, 0, 0), key = philox_key[r]): i = the high 64 bits of
 // (x0 | x1 << 32) * n, u = numpy rand()'s 53-bit double of (x2, x3).  One
