@@ -518,6 +518,28 @@ int mjx_mt_jump_table(int64_t n, int k, int G, uint64_t* table);
 int mjx_hpr_refresh_masks_jump(const uint32_t* state_in, const int32_t* ln_in, uint32_t* state_out,
                                int32_t* ln_out, int64_t n, int k, int G, const uint64_t* table,
                                const double* thresh, uint8_t* mask, void* stream);
+/* mjx_hpr_refresh_masks_jump for `instances` independent streams at once (HPR on
+ * a union of graphs, one torch CPU generator per instance): instance g's engine
+ * is state_in + 624 g and ln_in + 2 g (likewise the outputs), continued by
+ * `chunks` workgroups as above; each instance may stand anywhere in its 624-word
+ * block.  thresh[k] is shared (the instances walk t in lockstep), and so is
+ * `table`, which is mjx_mt_jump_table(n, k, chunks).  Row `it` of the mask holds
+ * every instance's decisions: mask[(it * instances + g) * n + i]. */
+int mjx_hpr_refresh_masks_jump_batch(const uint32_t* state_in, const int32_t* ln_in, uint32_t* state_out,
+                                     int32_t* ln_out, int64_t n, int k, int chunks, int64_t instances,
+                                     const uint64_t* table, const double* thresh, uint8_t* mask, void* stream);
+/* The consensus test and stop of the HPR loop (code/HPR_pytorch_RRG.py:352-356)
+ * for the G instances of a union graph, on the device.  bits: the node-packed
+ * end state of the rollout (G*n bits, instance g = bits [g*n, (g+1)*n)), s[G*n]
+ * the trial configuration, t = (*t_base, device, nullable = 0) + t_add the
+ * iteration reached.  counts[g] = the +1 bits of instance g's range.  With o =
+ * inst[g] (nullable: o = g), an instance with done[o] == 0 stops if t > TT
+ * (done[o] = 2), else if counts[g] == n (done[o] = 1): t_stop[o] = t,
+ * conf[o*n .. o*n+n) = its slice of s, *live drops by one.  An instance with
+ * done[o] != 0 is never written again. */
+int mjx_hpr_batch_record(const uint64_t* bits, const int32_t* s, int64_t n, int64_t G, const int32_t* inst,
+                         const int64_t* t_base, int64_t t_add, int64_t TT, unsigned long long* counts,
+                         int32_t* done, int64_t* t_stop, int32_t* conf, unsigned long long* live, void* stream);
 /* The edge half of marginals_comp (code/HPR_pytorch_RRG.py:150-161) alone:
  * zwork[4E] = per-row normalised (Z+ [2E], Z- [2E]) of every directed row. */
 int mjx_hpr_edge_z(int dtype, const void* chi, int64_t E, int p, int c, double eps, void* zwork,

@@ -17,7 +17,8 @@ from .dynamics import onestep_majority, s_endstate, m, pack, unpack, rollout, po
 from .attractor import attractor, random_spins, consensus_curve
 from .sa import SAReplicas, E_delta, sa_run, schedule_constants
 from .sa_er import SAReplicasER, sa_er_run
-from .hpr import HPRPlan, HPRState, HPr_dp, marginals_comp, new_biases_i, hpr_run
+from .hpr import HPRPlan, HPRState, HPr_dp, marginals_comp, new_biases_i, hpr_run, hpr_plan_indices
+from .hpr_batch import HPRBatch, hpr_batch_layout, hpr_run_batch
 from .hpr_er import HPRERPlan, HPr_dp_er, marginals_comp_er, hpr_er_plan, hpr_er_run
 from .bdcm import plan_indices as bdcm_plan_indices
 from .bdcm import (BDCMPlan, bdcm_er_plan, BDCM_ER, bdcm_leaf_reset, Zij, Zi_ER, phi_BP_GENERAL_ER,
@@ -34,7 +35,8 @@ __all__ = [
     "attractor", "random_spins", "consensus_curve",
     "SAReplicas", "E_delta", "sa_run", "schedule_constants",
     "SAReplicasER", "sa_er_run",
-    "HPRPlan", "HPRState", "HPr_dp", "marginals_comp", "new_biases_i", "hpr_run",
+    "HPRPlan", "HPRState", "HPr_dp", "marginals_comp", "new_biases_i", "hpr_run", "hpr_plan_indices",
+    "HPRBatch", "hpr_batch_layout", "hpr_run_batch",
     "HPRERPlan", "HPr_dp_er", "marginals_comp_er", "hpr_er_plan", "hpr_er_run",
     "BDCMPlan", "bdcm_plan_indices", "bdcm_er_plan", "BDCM_ER", "bdcm_converge", "bdcm_leaf_reset", "Zij", "Zi_ER", "phi_BP_GENERAL_ER",
     "avg_m_init_GENERAL_ER", "BDCM_entropy_procedure_GENERAL_ER", "bdcm_er_run", "drop_in",

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mjx_mt_jump_table_words": [c_i64, c_int, c_int],
     "mjx_mt_jump_table": [c_i64, c_int, c_int, c_vp],
     "mjx_hpr_refresh_masks_jump": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp],
+    "mjx_hpr_refresh_masks_jump_batch": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp],
+    "mjx_hpr_batch_record": [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_hpr_edge_z": [c_int, c_vp, c_i64, c_int, c_int, c_dbl, c_vp, c_vp],
     "mjx_hpr_node_biases": [c_int, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp],
     "mjx_hpr_q_supported": [c_int, c_int, c_int, c_int],

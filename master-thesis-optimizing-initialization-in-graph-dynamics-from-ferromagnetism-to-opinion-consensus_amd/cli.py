@@ -10,7 +10,9 @@ and write its np.savez keys.
         done, near_ties, wall_s, row_ptr, col, n_iso
   hpr   code/HPR_pytorch_RRG.py:224-237 (n, d, p, c, damppar, attr_value,
         lmbd_in, pie, gamma, TT) and :251 (n_rep), output :377
-        ("hpr_d{d}_p{p}.npz": mag_reached, conf, num_steps, graphs, time)
+        ("hpr_d{d}_p{p}.npz": mag_reached, conf, num_steps, graphs, time);
+        ``--batch B`` runs the replicas B at a time as one union graph
+        (hpr_batch.hpr_run_batch), the same arrays
   bdcm  code/ER_BDCM_entropy.ipynb raw lines 456-481 (n, deg, num_rep, p, c,
         eps, damppar, attr_value, epsilon, T_max, a, dl), output :515
         ("ER_p{p}.npz": m_init, ent1, ent, ... T_max, num_rep)
@@ -114,6 +116,8 @@ def build_parser():
         hp.add_argument(f"--{k}", type=(int if k == "lmbd_in" else type(v)), default=v)
     hp.add_argument("--dtype", choices=("float32", "float64"), default="float32",
                     help="message precision (the reference's is float64, :11)")
+    hp.add_argument("--batch", type=int, default=0,
+                    help="run that many replicas at a time as one union graph (0: one after the other); same output")
     _common(hp)
     bd = sub.add_parser("bdcm", help="code/ER_BDCM_entropy.ipynb")
     for k, v in BDCM_DEFAULTS.items():
@@ -223,6 +227,7 @@ def run_hpr(a):
     import torch
     from .graph import random_regular_edges
     from .hpr import hpr_run
+    from .hpr_batch import hpr_run_batch
     from .npz import save_hpr_npz
     R = a.replicas if a.replicas is not None else a.n_rep
     gs = a.graph_seed if a.graph_seed is not None else a.seed
@@ -231,7 +236,17 @@ def run_hpr(a):
     res = {"mag_reached": np.zeros(R), "num_steps": np.zeros(R), "conf": np.zeros((R, a.n)),
            "graphs": np.zeros((R, a.n, a.d))}
     t0 = time.time()
-    for k in range(R):                      # HPR_pytorch_RRG.py:259, one graph per replica
+    B = max(0, a.batch)
+    for j, k0 in enumerate(range(0, R, B) if B else ()):
+        # replicas k0 .. k0+B-1 as one union graph, consecutive groups round-robin over the devices
+        ks = list(range(k0, min(R, k0 + B)))
+        with torch.cuda.device(devs[j % len(devs)]):
+            r = hpr_run_batch(a.d, a.n, a.p, a.c, [random_regular_edges(a.d, a.n, seed=gs + k) for k in ks],
+                              [a.seed + k for k in ks], damppar=a.damppar, attr_value=a.attr_value,
+                              lmbd_in=a.lmbd_in, pie=a.pie, gamma=a.gamma, TT=a.TT, dtype=dtype)
+        for key in res:
+            res[key][ks] = r[key]
+    for k in (() if B else range(R)):       # HPR_pytorch_RRG.py:259, one graph per replica
         with torch.cuda.device(devs[k % len(devs)]):
             edges = random_regular_edges(a.d, a.n, seed=gs + k)
             r = hpr_run(a.d, a.n, a.p, a.c, damppar=a.damppar, attr_value=a.attr_value, lmbd_in=a.lmbd_in,

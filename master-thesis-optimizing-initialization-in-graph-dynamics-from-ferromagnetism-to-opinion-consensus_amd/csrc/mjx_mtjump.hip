@@ -189,13 +189,19 @@ constexpr int kThreads = 640;
 // Workgroup j: words [jL, (j+1)L) of the batch, counted from word 0 of the
 // batch-start buffer (state_in; the first word read is 625 - left).  Pair p
 // (words first + 2p, first + 2p + 1) is uniform p = iteration p / n, node p % n.
-__global__ void __launch_bounds__(kThreads) k_mt_refresh_jump(const uint32_t* __restrict__ state_in,
-                                                              const int32_t* __restrict__ ln_in,
-                                                              uint32_t* __restrict__ state_out,
-                                                              int32_t* __restrict__ ln_out, int64_t n, int64_t E,
-                                                              int64_t L, const uint64_t* __restrict__ table,
-                                                              const double* __restrict__ thresh,
-                                                              uint8_t* __restrict__ mask) {
+//
+// kBatch: one of `ninst` independent streams (instance `inst` of a union of
+// graphs, mjx_hpr_refresh_masks_jump_batch): the pointers are the instance's
+// own state and counters, and iteration `it`'s row of the mask holds every
+// instance's n decisions, this one's at (it * ninst + inst) * n.
+template <bool kBatch>
+__device__ __forceinline__ void mt_refresh_jump_body(const uint32_t* __restrict__ state_in,
+                                                     const int32_t* __restrict__ ln_in,
+                                                     uint32_t* __restrict__ state_out, int32_t* __restrict__ ln_out,
+                                                     int64_t n, int64_t E, int64_t L,
+                                                     const uint64_t* __restrict__ table,
+                                                     const double* __restrict__ thresh, uint8_t* __restrict__ mask,
+                                                     int64_t inst, int64_t ninst) {
     extern __shared__ __align__(16) uint32_t smem[];
     uint32_t* S = smem;                       // the stream x_0 .. x_{kStream-1} (jumping workgroups)
     uint32_t* blk = smem + kStream + 1;       // two 624-word blocks, ping-pong
@@ -275,7 +281,9 @@ __global__ void __launch_bounds__(kThreads) k_mt_refresh_jump(const uint32_t* __
             const uint64_t r = ((uint64_t)yh << 32) | yl;
             const double u = (double)(r & ((1ull << 53) - 1)) * (1.0 / 9007199254740992.0);
             const int64_t it = p / n;
-            mask[p] = u < thresh[it] ? 1 : 0;
+            const uint8_t m = u < thresh[it] ? 1 : 0;
+            if constexpr (kBatch) mask[(it * ninst + inst) * n + (p - it * n)] = m;
+            else mask[p] = m;
         }
         // the engine's state after the batch: the block holding the last word read
         if (last - 1 >= b0 && last - 1 < b0 + kN) {
@@ -291,6 +299,34 @@ __global__ void __launch_bounds__(kThreads) k_mt_refresh_jump(const uint32_t* __
         cur = nxt;
         nxt = t;
     }
+}
+
+__global__ void __launch_bounds__(kThreads) k_mt_refresh_jump(const uint32_t* __restrict__ state_in,
+                                                              const int32_t* __restrict__ ln_in,
+                                                              uint32_t* __restrict__ state_out,
+                                                              int32_t* __restrict__ ln_out, int64_t n, int64_t E,
+                                                              int64_t L, const uint64_t* __restrict__ table,
+                                                              const double* __restrict__ thresh,
+                                                              uint8_t* __restrict__ mask) {
+    mt_refresh_jump_body<false>(state_in, ln_in, state_out, ln_out, n, E, L, table, thresh, mask, 0, 1);
+}
+
+// k_mt_refresh_jump with an instance dimension on the grid: workgroup (j, g) is
+// chunk j of instance g's stream (state + 624 g, left/next + 2 g, in and out).
+// Each instance starts wherever its engine stands in its 624-word block (its
+// own `left`), so which chunks hold words of its batch differs per instance;
+// the thresholds and the jump table (a function of n, k and the chunk count
+// only) are shared.
+__global__ void __launch_bounds__(kThreads) k_mt_refresh_jump_batch(const uint32_t* __restrict__ state_in,
+                                                                    const int32_t* __restrict__ ln_in,
+                                                                    uint32_t* __restrict__ state_out,
+                                                                    int32_t* __restrict__ ln_out, int64_t n, int64_t E,
+                                                                    int64_t L, const uint64_t* __restrict__ table,
+                                                                    const double* __restrict__ thresh,
+                                                                    uint8_t* __restrict__ mask) {
+    const int64_t g = blockIdx.y;
+    mt_refresh_jump_body<true>(state_in + g * kN, ln_in + 2 * g, state_out + g * kN, ln_out + 2 * g, n, E, L, table,
+                               thresh, mask, g, gridDim.y);
 }
 
 }  // namespace mtj
@@ -353,5 +389,26 @@ extern "C" int mjx_hpr_refresh_masks_jump(const uint32_t* state_in, const int32_
     mtj::k_mt_refresh_jump<<<(unsigned)g.G, mtj::kThreads, lds, as_stream(stream)>>>(
         state_in, ln_in, state_out, ln_out, n, g.E, g.L, table, thresh, mask);
     MJX_LAUNCH_CHECK("k_mt_refresh_jump");
+    return MJX_OK;
+}
+
+extern "C" int mjx_hpr_refresh_masks_jump_batch(const uint32_t* state_in, const int32_t* ln_in, uint32_t* state_out,
+                                                int32_t* ln_out, int64_t n, int k, int chunks, int64_t instances,
+                                                const uint64_t* table, const double* thresh, uint8_t* mask,
+                                                void* stream) {
+    if (n < 1 || k < 0 || instances < 0 || instances > 65535 || !state_in || !ln_in || !state_out || !ln_out ||
+        state_in == state_out || (k > 0 && (!thresh || !mask)))
+        return MJX_EINVAL;
+    if (k == 0 || instances == 0) return MJX_OK;
+    mtj::Geo g;
+    if (!mtj::geometry(n, k, chunks, &g)) return MJX_EINVAL;
+    if (g.G > 1 && !table) return MJX_EINVAL;
+    const size_t lds = sizeof(uint32_t) * (size_t)(mtj::kStream + 1 + 2 * mtj::kN);
+    MJX_HIP(hipFuncSetAttribute((const void*)mtj::k_mt_refresh_jump_batch, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds),
+            "mt_jump_batch lds");
+    mtj::k_mt_refresh_jump_batch<<<dim3((unsigned)g.G, (unsigned)instances), mtj::kThreads, lds, as_stream(stream)>>>(
+        state_in, ln_in, state_out, ln_out, n, g.E, g.L, table, thresh, mask);
+    MJX_LAUNCH_CHECK("k_mt_refresh_jump_batch");
     return MJX_OK;
 }

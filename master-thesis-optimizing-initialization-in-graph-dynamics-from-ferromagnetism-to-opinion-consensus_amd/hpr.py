@@ -40,6 +40,42 @@ def _code(dtype):
         raise _lib.MjxError(f"HPR messages must be float32 or float64, got {dtype}") from None
 
 
+def hpr_plan_indices(edges, n, d, nbrs=None):
+    """Host index arrays of a d-regular graph for the HPR kernels (numpy only):
+    (edges (E, 2), nbrs (n, d), out_row (n, d), in_row (n, d)), all int64 --
+    what HPRPlan puts on the device."""
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    n, d = int(n), int(d)
+    E = e.shape[0]
+    if 2 * E != n * d:
+        raise ValueError(f"{E} edges is not a {d}-regular graph on {n} nodes")
+    u, v = e[:, 0], e[:, 1]
+    if nbrs is None:
+        src = np.concatenate([u, v])
+        dst = np.concatenate([v, u])
+        order = np.lexsort((dst, src))
+        nbrs = dst[order].reshape(n, d)
+        if not np.array_equal(src[order], np.repeat(np.arange(n), d)):
+            raise ValueError("graph is not d-regular")
+    nbrs = np.asarray(nbrs, dtype=np.int64).reshape(n, d)
+    # row of the directed message x -> y: r for (u_r, v_r), r + E for (v_r, u_r)
+    keys = np.concatenate([u * n + v, v * n + u])
+    rows = np.concatenate([np.arange(E), np.arange(E) + E])
+    srt = np.argsort(keys, kind="stable")
+    keys, rows = keys[srt], rows[srt]
+
+    def row_of(x, y):
+        k = x * n + y
+        pos = np.searchsorted(keys, k)
+        if np.any(pos >= keys.size) or np.any(keys[np.minimum(pos, keys.size - 1)] != k):
+            raise ValueError("neighbour array inconsistent with the edge list")
+        return rows[pos]
+
+    a = np.repeat(np.arange(n, dtype=np.int64), d)
+    k = nbrs.reshape(-1)
+    return e, nbrs, row_of(a, k).reshape(n, d), row_of(k, a).reshape(n, d)      # out_row: N_edges_pos (:110-118)
+
+
 class HPRPlan:
     """Device-resident index plan of a d-regular graph for the HPR kernels.
 
@@ -47,43 +83,18 @@ class HPRPlan:
     nbrs:  (n, d) neighbours of each node in G.neighbors order (the reference's
            N_nodes, code/HPR_pytorch_RRG.py:110-118); optional, any order gives
            the same messages up to floating-point summation order.
+    indices: the result of hpr_plan_indices for this graph, if the caller has
+           it already (the union of a batch, hpr_batch.py).
     """
 
-    def __init__(self, edges, n, d, nbrs=None):
-        e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    def __init__(self, edges, n, d, nbrs=None, indices=None):
         n, d = int(n), int(d)
-        E = e.shape[0]
-        if 2 * E != n * d:
-            raise ValueError(f"{E} edges is not a {d}-regular graph on {n} nodes")
-        u, v = e[:, 0], e[:, 1]
-        if nbrs is None:
-            src = np.concatenate([u, v])
-            dst = np.concatenate([v, u])
-            order = np.lexsort((dst, src))
-            nbrs = dst[order].reshape(n, d)
-            if not np.array_equal(src[order], np.repeat(np.arange(n), d)):
-                raise ValueError("graph is not d-regular")
-        nbrs = np.asarray(nbrs, dtype=np.int64).reshape(n, d)
-        # row of the directed message x -> y: r for (u_r, v_r), r + E for (v_r, u_r)
-        keys = np.concatenate([u * n + v, v * n + u])
-        rows = np.concatenate([np.arange(E), np.arange(E) + E])
-        srt = np.argsort(keys, kind="stable")
-        keys, rows = keys[srt], rows[srt]
-
-        def row_of(x, y):
-            k = x * n + y
-            pos = np.searchsorted(keys, k)
-            if np.any(pos >= keys.size) or np.any(keys[np.minimum(pos, keys.size - 1)] != k):
-                raise ValueError("neighbour array inconsistent with the edge list")
-            return rows[pos]
-
-        a = np.repeat(np.arange(n, dtype=np.int64), d)
-        k = nbrs.reshape(-1)
-        self.n, self.d, self.E = n, d, E
+        e, nbrs, out_row, in_row = hpr_plan_indices(edges, n, d, nbrs) if indices is None else indices
+        self.n, self.d, self.E = n, d, e.shape[0]
         self.edges = e
         self.nbrs_host = nbrs
-        self.out_row_host = row_of(a, k).reshape(n, d)      # N_edges_pos (:110-118)
-        self.in_row_host = row_of(k, a).reshape(n, d)
+        self.out_row_host = out_row
+        self.in_row_host = in_row
         dev = _device.require_gpu()
         self.nbr = torch.from_numpy(nbrs.astype(np.int32).reshape(-1)).to(dev)
         self.in_row = torch.from_numpy(self.in_row_host.astype(np.int32).reshape(-1)).to(dev)
