@@ -766,6 +766,72 @@ int mjx_bdcm_edge_obs_batch(const double* chi, const int32_t* fwd_row, const int
 int mjx_segsum_f64(const double* x, const int64_t* seg_ptr, int64_t G, int take_log, double* work, double* out,
                    void* stream);
 
+/* ---- flip gains and the greedy quench (no reference counterpart) --------- */
+/*
+ * G is an ELL or CSR graph with SYMMETRIC adjacency (as a multiset of directed
+ * entries, the precondition of the light-cone calls above); row entries count
+ * with multiplicity, a degree-0 node keeps its spin, the rule is sign(2S+s).
+ * With T = p + c - 1, s_end = onestep^T(s), F(s) = sum s_end and s^i = s with
+ * spin i flipped, for every replica r and node i:
+ *   gain[r, i]   = F(s^i) - F(s): int32, even, |gain| <= 2n;
+ *   consensus[r] = (F(s) = n);
+ *   removable bit (i, r) = 1 iff s_i = +1, consensus[r] and F(s^i) = n; packed
+ *     like the state (n * W words, W = ceil(R/64)); padding replicas stay 0;
+ *   quench(s, order): every replica with consensus[r] visits i = order[0], ...,
+ *     order[n-1] and, if s_i = +1 and onestep^T(s^i) is all +1, sets s <- s^i;
+ *     a replica without consensus is returned unchanged; flipped[r] counts the
+ *     spins turned.
+ * Monotonicity: the rule is non-decreasing in every input, so s' <= s implies
+ * onestep^T(s') <= onestep^T(s).  Hence (1) a node not removable in s is not
+ * removable in any s' <= s; (2) one quench pass ends in a state whose
+ * removable mask is empty, and a second pass flips nothing; (3) only nodes of
+ * the initial removable mask can ever be flipped, so the pass visits only
+ * those, in `order` order.
+ *
+ * levels: HOST array of T+1 device pointers, levels[t] = onestep^t(s) as
+ * replica-packed words (n * W each; levels[0] = s); padding replicas 0 in all
+ * of them.  caps: HOST int64 [T+1], the ball bound of the graph
+ * (mjx_sa_csr_ball_bound, or mjx_ell_ball_bound = min(n, sum_{k<=t} d^k) for an
+ * (n, d) neighbour array): the lists of level t never outgrow caps[t].  A wave
+ * evaluates one (node, word column) pair; the first lds_entries entries of each
+ * of its T+2 lists live in LDS (0 = the library's choice, 64), the rest in its
+ * part of `scratch`.  mjx_quench_lds: LDS bytes of a workgroup (-1: T or
+ * lds_entries out of range, more than 64 KiB).  _scratch_bytes: bytes of
+ * `scratch` (always > 0: it starts with a header of 1 + 65 W words; -1 on bad
+ * arguments).  After the call word 0 of `scratch` is nonzero iff a list outgrew
+ * wrong caps (nothing is written out of bounds, the results are then void).
+ *
+ * mjx_flip_gain_*: all pairs in parallel, the levels are only read.  Writes
+ * removable[n * W], consensus[R] (bytes 0 / 1) and, when `gain` is not NULL,
+ * gain as int32 [n][64 W] NODE-major: gain[i * 64 W + r] (r >= R: 0).
+ * mjx_quench_*: one workgroup per word column walks cand[cand_ptr[w] ..
+ * cand_ptr[w+1]) (device arrays: the nodes with a removable bit in column w, in
+ * `order` order) and commits every accepted flip into all T+1 levels IN PLACE
+ * (the caller passes copies); writes consensus[R] (of the state as passed) and
+ * flipped[64 W].
+ * MJX_EINVAL: T outside 0..6, n < 1 or n >= 2^31, R < 1, a NULL required
+ * pointer, scratch_bytes below _scratch_bytes.  No allocation, no host
+ * synchronisation.
+ */
+int mjx_ell_ball_bound(int64_t n, int d, int T, int64_t* bound_out);
+int64_t mjx_quench_lds(int T, int lds_entries);
+int64_t mjx_flip_gain_scratch_bytes(int64_t n, int64_t R, int T, const int64_t* caps, int lds_entries);
+int64_t mjx_quench_scratch_bytes(int64_t R, int T, const int64_t* caps, int lds_entries);
+int mjx_flip_gain_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c,
+                         const uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                         int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus, int32_t* gain, void* stream);
+int mjx_flip_gain_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                         const uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                         int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus, int32_t* gain, void* stream);
+int mjx_quench_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c, uint64_t* const* levels,
+                      const int64_t* caps, int lds_entries, void* scratch, int64_t scratch_bytes,
+                      const int32_t* cand, const int64_t* cand_ptr, uint8_t* consensus, int64_t* flipped,
+                      void* stream);
+int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                      uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                      int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr, uint8_t* consensus,
+                      int64_t* flipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

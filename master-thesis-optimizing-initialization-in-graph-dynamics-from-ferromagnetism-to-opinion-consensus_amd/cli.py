@@ -1,4 +1,4 @@
-"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm`` run the reference's three
+"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm|attractor|quench`` run the reference's three
 experiments with its module constants as flags -- same names, same defaults --
 and write its np.savez keys.
 
@@ -20,6 +20,11 @@ and write its np.savez keys.
         (attractor.consensus_curve) on one random regular or Erdos-Renyi
         graph; output "attractor_{graph}.npz": m_init, consensus, c1, c2,
         unsettled, p, c, sum_att, init_plus
+  quench  no reference script: the greedy zero-temperature clean-up
+        (quench.quench) of the ``conf`` of an SA / HPR result file (``graphs``:
+        one graph per replica, run replica by replica) or an sa-er file
+        (``row_ptr``, ``col``: one call); output: the input's arrays plus
+        conf_quenched, mag_quenched, flipped, consensus
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -138,6 +143,14 @@ def build_parser():
     at.add_argument("--chunk", type=int, default=16, help="sweeps between two host reads of the unsettled counter")
     at.add_argument("--batch", type=int, default=None, help="m_inits per replica-packed batch (default: all)")
     _common(at)
+    qu = sub.add_parser("quench", help="drop the +1 spins a consensus configuration does not need (no reference script)")
+    qu.add_argument("--in", dest="inp", required=True, help="result .npz of sa / hpr (graphs, conf) or sa-er "
+                                                             "(row_ptr, col, conf)")
+    qu.add_argument("--p", type=int, required=True)
+    qu.add_argument("--c", type=int, required=True)
+    qu.add_argument("--order-seed", type=int, default=None,
+                    help="visit the nodes in np.random.default_rng(S).permutation(n) order (default: 0, 1, ...)")
+    qu.add_argument("--out", default=None, help="output .npz (default: the input's name + _quenched)")
     return ap
 
 
@@ -295,9 +308,39 @@ def run_attractor(a):
     return res
 
 
+def run_quench(a):
+    from .graph import Graph
+    from .quench import quench
+    t0 = time.time()
+    with np.load(a.inp, allow_pickle=False) as z:
+        res = {k: z[k] for k in z.files}
+    if "conf" not in res or not ("graphs" in res or ("row_ptr" in res and "col" in res)):
+        raise SystemExit(f"{a.inp}: need conf with graphs (sa / hpr files) or with row_ptr, col (sa-er files)")
+    conf = np.atleast_2d(res["conf"])
+    S = conf.astype(np.int64)                   # the result files hold +-1 as floats
+    if "graphs" in res:
+        # one graph per replica (code/SA_RRG.py:58-62): replica by replica
+        if res["graphs"].shape[0] != S.shape[0]:
+            raise SystemExit(f"{a.inp}: {res['graphs'].shape[0]} graphs for {S.shape[0]} configurations")
+        runs = [quench(res["graphs"][k].astype(np.int32), S[k:k + 1], a.p, a.c, seed=a.order_seed)
+                for k in range(S.shape[0])]
+        q = {k: np.concatenate([r[k] for r in runs]) for k in ("conf", "mag", "flipped", "consensus")}
+    else:
+        q = quench(Graph.csr(res["row_ptr"], res["col"]), S, a.p, a.c, seed=a.order_seed)
+    res["conf_quenched"] = q["conf"].astype(conf.dtype)
+    res["mag_quenched"], res["flipped"], res["consensus"] = q["mag"], q["flipped"], q["consensus"]
+    out = a.out or (a.inp[:-4] if a.inp.endswith(".npz") else a.inp) + "_quenched.npz"
+    np.savez(out, **res)
+    print(f"quench: {S.shape[0]} replicas, consensus {res['consensus'].astype(int).tolist()}, flipped "
+          f"{res['flipped'].tolist()}, mag {np.round(S.mean(axis=1), 4).tolist()} -> "
+          f"{np.round(res['mag_quenched'], 4).tolist()}, {time.time() - t0:.1f} s -> {out}", flush=True)
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm, "attractor": run_attractor}[a.cmd](a)
+    return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm, "attractor": run_attractor,
+            "quench": run_quench}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,503 @@
+// Flip gains and the greedy quench (no reference counterpart; definitions in
+// include/mjx.h): for every node i and replica r the change of F(s) = sum of
+// onestep^T(s) when spin i alone is flipped, the mask of +1 spins a consensus
+// replica can drop, and the sequential zero-temperature pass that drops them.
+//
+// One evaluator serves all of it.  A wave owns one (node i, word column) pair:
+// the 64 replicas of the column are the 64 bits of every word it touches, its
+// 64 lanes share the candidates of a level.  With the cached levels L_0 = s,
+// L_t = onestep^t(s) the flip is a level-0 difference {i: d0}; level t
+// recomputes only the nodes changed at level t-1 and the nodes of their rows
+// (the adjacency is symmetric, so row(v) lists every node that reads v) from
+// L_{t-1}[k] ^ diff_{t-1}[k] with the bit-sliced majority of mjx_common.h and
+// keeps (node, diff word) where the result differs from L_t.  The lists are
+// the union over the column's replicas, so they are bounded by the ball bound
+// (mjx_sa_csr_ball_bound; min(n, sum_{k<=t} d^k) on a d-regular graph).  Entry
+// q of a list lives in LDS for q < E and in the wave's part of the caller's
+// scratch area beyond; nothing is truncated.
+//
+// The wave is the whole workgroup, so the lanes see each other's plain stores
+// to LDS, scratch and (quench) the levels after a workgroup barrier: one CU,
+// one vector L1.  Everything is integer; no flags needed.
+#include "mjx_common.h"
+#include <algorithm>
+
+namespace mjx {
+
+constexpr int QN_MAXT = 6;
+constexpr int QN_LDS_DEFAULT = 64;            // list entries kept in LDS (lds_entries = 0)
+constexpr size_t kQnLdsMax = 64 * 1024;       // no dynamic-LDS opt-in needed
+constexpr int64_t kQnMaxBlocks = 8192;        // flip-gain grid: 32 waves on each of 256 CUs
+
+struct QnCone {
+    u64* L[QN_MAXT + 1];          // L[t] = onestep^t(s); word (v, col) at v*W + col
+    int E;                        // entries per list in LDS
+    int cap[QN_MAXT + 2];         // capacity of list l: changed nodes of level l (l <= T), candidates (l = T+1)
+    int64_t soff[QN_MAXT + 2];    // first scratch slot of list l
+    int64_t Sd;                   // scratch slots of the T+1 change lists of a workgroup
+    int64_t Sc;                   // scratch slots of its candidate list
+    int64_t stride;               // bytes of scratch per workgroup (multiple of 8)
+    unsigned char* lists;         // scratch behind the header
+    u64* header;                  // [0] overflow flag, [1, 1+64W) +1 counts of L_T, [1+64W, 1+65W) consensus words
+};
+
+struct AdjEll {
+    const int32_t* adj;
+    int d;
+    __device__ __forceinline__ int deg(uint32_t) const { return d; }
+    __device__ __forceinline__ uint32_t nbr(uint32_t v, int e) const { return (uint32_t)adj[(int64_t)v * d + e]; }
+    __device__ __forceinline__ int fixed() const { return d; }
+};
+
+struct AdjCsr {
+    const int64_t* row_ptr;
+    const int32_t* col;
+    __device__ __forceinline__ int deg(uint32_t v) const { return (int)(row_ptr[v + 1] - row_ptr[v]); }
+    __device__ __forceinline__ uint32_t nbr(uint32_t v, int e) const { return (uint32_t)col[row_ptr[v] + e]; }
+    __device__ __forceinline__ int fixed() const { return 0; }
+};
+
+// The lists of one workgroup (= one wave): LDS part and scratch part.
+struct QnLists {
+    u64* ldiff;                   // LDS [(T+1)][E]
+    uint32_t* lnode;              // LDS [(T+1)][E]
+    uint32_t* lcand;              // LDS [E]
+    u64* sdiff;                   // scratch [Sd]
+    uint32_t* snode;              // scratch [Sd]
+    uint32_t* scand;              // scratch [Sc]
+    int E;
+    const int64_t* soff;
+    __device__ __forceinline__ uint32_t node(int l, int q) const {
+        return q < E ? lnode[l * E + q] : snode[soff[l] + (q - E)];
+    }
+    __device__ __forceinline__ u64 diff(int l, int q) const {
+        return q < E ? ldiff[l * E + q] : sdiff[soff[l] + (q - E)];
+    }
+    __device__ __forceinline__ void put(int l, int q, uint32_t v, u64 dw) const {
+        if (q < E) { lnode[l * E + q] = v; ldiff[l * E + q] = dw; }
+        else { snode[soff[l] + (q - E)] = v; sdiff[soff[l] + (q - E)] = dw; }
+    }
+    __device__ __forceinline__ uint32_t cand(int q) const { return q < E ? lcand[q] : scand[q - E]; }
+    __device__ __forceinline__ void put_cand(int q, uint32_t v) const {
+        if (q < E) lcand[q] = v;
+        else scand[q - E] = v;
+    }
+};
+
+__device__ __forceinline__ QnLists qn_lists(const QnCone& C, int T, unsigned char* lds, int64_t wg) {
+    QnLists S;
+    S.E = C.E;
+    S.soff = C.soff;
+    S.ldiff = (u64*)lds;
+    S.lnode = (uint32_t*)(S.ldiff + (size_t)(T + 1) * C.E);
+    S.lcand = S.lnode + (size_t)(T + 1) * C.E;
+    unsigned char* base = C.lists + wg * C.stride;
+    S.sdiff = (u64*)base;
+    S.snode = (uint32_t*)(S.sdiff + C.Sd);
+    S.scand = S.snode + C.Sd;
+    return S;
+}
+
+constexpr uint32_t kQnNoNode = 0xffffffffu;    // never a node (n < 2^31)
+
+// register of lane m (wave-uniform m)
+__device__ __forceinline__ uint32_t qn_lane32(uint32_t x, int m) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, m);
+}
+__device__ __forceinline__ u64 qn_lane64(u64 x, int m) {
+    return (u64)qn_lane32((uint32_t)x, m) | ((u64)qn_lane32((uint32_t)(x >> 32), m) << 32);
+}
+
+// Difference word of node k in change list l (np entries; 0 when it has none),
+// for every lane's own k at once: the lanes load 64 entries together and the
+// entries are then broadcast from registers, so the scan waits for LDS once per
+// 64 entries, not once per entry.  Wave-uniform call; k = kQnNoNode gives 0.
+__device__ __forceinline__ u64 qn_patch(const QnLists& S, int l, int np, uint32_t k) {
+    const int lane = threadIdx.x;
+    u64 x = 0;
+    for (int b = 0; b < np; b += 64) {
+        const bool in = b + lane < np;
+        const uint32_t ln = in ? S.node(l, b + lane) : 0xfffffffeu;
+        const u64 ld = in ? S.diff(l, b + lane) : 0;
+        const int cc = (np - b) < 64 ? (np - b) : 64;
+        for (int m = 0; m < cc; ++m) {
+            const uint32_t nq = qn_lane32(ln, m);
+            const u64 dq = qn_lane64(ld, m);
+            x ^= (k == nq) ? dq : 0;
+        }
+    }
+    return x;
+}
+
+// New word at level lv of every lane's candidate j (kQnNoNode: none) from level
+// lv-1 with the change list applied.  Wave-uniform call.
+template <class Adj>
+__device__ __forceinline__ u64 qn_new_word(const Adj& A, const QnLists& S, const u64* Lp, int64_t W, int64_t col,
+                                           int lv, int np, uint32_t j) {
+    const bool has = j != kQnNoNode;
+    auto word = [&](uint32_t k) -> u64 {
+        return (k != kQnNoNode ? Lp[(int64_t)k * W + col] : 0) ^ qn_patch(S, lv - 1, np, k);
+    };
+    const u64 own = word(j);
+    if (A.fixed() == 3) {
+        u64 x[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) x[e] = word(has ? A.nbr(j, e) : kQnNoNode);
+        return majority_fixed<3>(x, own);
+    }
+    if (A.fixed() == 4) {
+        u64 x[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = word(has ? A.nbr(j, e) : kQnNoNode);
+        return majority_fixed<4>(x, own);
+    }
+    const int dg = has ? A.deg(j) : 0;
+    int longest = dg;
+    for (int off = 32; off; off >>= 1) {
+        const int o = __shfl_xor(longest, off);
+        longest = o > longest ? o : longest;
+    }
+    BitCounter<8> bc;                            // degree <= 255; degree 0 keeps the word
+    bc.reset();
+    for (int e = 0; e < longest; ++e) bc.add(word(e < dg ? A.nbr(j, e) : kQnNoNode));   // a lane past its row adds 0
+    return bc.majority(dg, own);
+}
+
+// Light cone of the level-0 difference {i: d0} in word column col.  On return
+// cnt[l] entries of list l (l = 0..T) hold the changed nodes of level l and
+// their difference words.  Wave-uniform control flow; all 64 lanes take part.
+// Returns false when a list outgrew its cap (caps not of this graph): nothing
+// is written out of bounds, the lists are then incomplete.
+template <class Adj>
+__device__ bool qn_cone(const Adj& A, const QnCone& C, const QnLists& S, int T, int64_t W, int64_t col, uint32_t i,
+                        u64 d0, int* cnt) {
+    const int lane = threadIdx.x;
+    const u64 below = (1ull << lane) - 1;
+    for (int l = 0; l <= T; ++l) cnt[l] = 0;
+    if (d0 == 0) return true;
+    if (lane == 0) S.put(0, 0, i, d0);
+    cnt[0] = 1;
+    __syncthreads();
+    bool ok = true;
+    for (int lv = 1; lv <= T && ok; ++lv) {
+        const int np = cnt[lv - 1];
+        if (np == 0) break;                                  // nothing propagates further
+        // candidates: the nodes changed at level lv-1 and the nodes of their rows, each once.
+        // A lane per changed node, the lanes walking their rows together: round e offers
+        // the node itself (e = 0) or entry e-1 of every lane's row, so a level costs
+        // (longest row + 1) rounds per 64 changed nodes, the rows' loads in flight together.
+        int nu = 0;
+        for (int base = 0; base < np && ok; base += 64) {
+            const bool have = base + lane < np;
+            const uint32_t v = have ? S.node(lv - 1, base + lane) : 0u;
+            const int dg = have ? A.deg(v) : -1;
+            int longest = dg;
+            for (int off = 32; off; off >>= 1) {
+                const int o = __shfl_xor(longest, off);
+                longest = o > longest ? o : longest;
+            }
+            const int lanes = (np - base) < 64 ? (np - base) : 64;
+            for (int e = 0; e <= longest && ok; ++e) {
+                const bool valid = e <= dg;
+                const uint32_t x = valid ? (e == 0 ? v : A.nbr(v, e - 1)) : kQnNoNode;
+                // bit m of seen: lane m's offer is a candidate already, or a lower lane offers it too
+                u64 seen = 0;
+                for (int m = 0; m < lanes; ++m) {
+                    const uint32_t y = qn_lane32(x, m);
+                    if (__ballot(x == y) & ((1ull << m) - 1)) seen |= 1ull << m;
+                }
+                for (int b = 0; b < nu; b += 64) {
+                    const uint32_t have_c = (b + lane < nu) ? S.cand(b + lane) : 0xfffffffeu;
+                    for (int m = 0; m < lanes; ++m) {
+                        const uint32_t y = qn_lane32(x, m);
+                        if (__ballot(have_c == y)) seen |= 1ull << m;
+                    }
+                }
+                const bool fresh = valid && !((seen >> lane) & 1);
+                const u64 mask = __ballot(fresh);
+                const int pos = nu + __popcll(mask & below);
+                const int total = nu + __popcll(mask);
+                if (total > C.cap[T + 1]) ok = false;
+                else if (fresh) S.put_cand(pos, x);
+                nu = ok ? total : nu;
+                __syncthreads();
+            }
+        }
+        // recompute the candidates; keep those whose word differs from the cached level
+        int nc = 0;
+        const u64* Lp = C.L[lv - 1];
+        const u64* Ln = C.L[lv];
+        for (int base = 0; base < nu && ok; base += 64) {
+            const int q = base + lane;
+            const uint32_t j = q < nu ? S.cand(q) : kQnNoNode;
+            const u64 nw = qn_new_word(A, S, Lp, W, col, lv, np, j);
+            const u64 dw = q < nu ? nw ^ Ln[(int64_t)j * W + col] : 0;
+            const u64 mask = __ballot(dw != 0);
+            const int pos = nc + __popcll(mask & below);
+            const int total = nc + __popcll(mask);
+            if (total > C.cap[lv]) ok = false;
+            else if (dw != 0) S.put(lv, pos, j, dw);
+            nc = ok ? total : nc;
+        }
+        cnt[lv] = nc;
+        __syncthreads();
+    }
+    return ok;
+}
+
+__device__ __forceinline__ u64 qn_valid(int64_t col, int64_t W, int64_t R) {
+    const int tail = (int)(R & 63);
+    return (col == W - 1 && tail) ? ((1ull << tail) - 1) : ~0ull;
+}
+
+// consensus[r] = (+1 count of L_T == n), and the same as a word per column
+__global__ void __launch_bounds__(64) k_qn_consensus(const u64* __restrict__ counts, int64_t n, int64_t R,
+                                                     u64* __restrict__ words, uint8_t* __restrict__ consensus) {
+    const int64_t r = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const bool c = r < R && counts[r] == (u64)n;
+    if (r < R) consensus[r] = c ? 1 : 0;
+    const u64 m = __ballot(c);
+    if (threadIdx.x == 0) words[blockIdx.x] = m;
+}
+
+template <class Adj>
+__global__ void __launch_bounds__(64) k_flip_gain(Adj A, QnCone C, int T, int64_t n, int64_t W, int64_t R,
+                                                  u64* __restrict__ removable, int32_t* __restrict__ gain) {
+    extern __shared__ __align__(8) unsigned char qn_lds[];
+    const QnLists S = qn_lists(C, T, qn_lds, blockIdx.x);
+    const int lane = threadIdx.x;
+    const u64* cons = C.header + 1 + 64 * W;
+    const int64_t pairs = n * W;
+    int cnt[QN_MAXT + 1];
+    for (int64_t pid = blockIdx.x; pid < pairs; pid += gridDim.x) {
+        const int64_t i = pid / W, col = pid - i * W;
+        const u64 valid = qn_valid(col, W, R);
+        const bool ok = qn_cone(A, C, S, T, W, col, (uint32_t)i, valid, cnt);
+        if (!ok) {
+            if (lane == 0) C.header[0] = 1;
+            break;
+        }
+        // the level-T entries, 64 at a time in registers: their OR, and per lane (= replica)
+        // +-2 for every entry that holds its bit
+        u64 orT = 0;
+        int g = 0;
+        for (int b = 0; b < cnt[T]; b += 64) {
+            const bool in = b + lane < cnt[T];
+            const u64 mine = in ? S.diff(T, b + lane) : 0;
+            const u64 was = (gain && in) ? C.L[T][(int64_t)S.node(T, b + lane) * W + col] : 0;
+            const int cc = (cnt[T] - b) < 64 ? (cnt[T] - b) : 64;
+            for (int m = 0; m < cc; ++m) {
+                const u64 dq = qn_lane64(mine, m), old = qn_lane64(was, m);
+                orT |= dq;
+                if ((dq >> lane) & 1) g += ((old >> lane) & 1) ? -2 : 2;
+            }
+        }
+        if (lane == 0) removable[pid] = C.L[0][pid] & cons[col] & ~orT & valid;
+        if (gain) gain[(i * W + col) * 64 + lane] = g;
+        __syncthreads();                                     // the lists are reused by the next pair
+    }
+}
+
+template <class Adj>
+__global__ void __launch_bounds__(64) k_quench(Adj A, QnCone C, int T, int64_t n, int64_t W, int64_t R,
+                                               const int32_t* __restrict__ cand, const int64_t* __restrict__ cand_ptr,
+                                               long long* __restrict__ flipped) {
+    extern __shared__ __align__(8) unsigned char qn_lds[];
+    const QnLists S = qn_lists(C, T, qn_lds, blockIdx.x);
+    const int lane = threadIdx.x;
+    const int64_t col = blockIdx.x;
+    const u64 valid = qn_valid(col, W, R);
+    const u64 cons = C.header[1 + 64 * W + col] & valid;
+    int cnt[QN_MAXT + 1];
+    long long mine = 0;
+    const int64_t c1 = cand_ptr[col + 1];
+    for (int64_t c = cand_ptr[col]; c < c1; ++c) {
+        const uint32_t i = (uint32_t)cand[c];
+        // the flip is tried in the replicas where it can count: s_i = +1 and consensus
+        const u64 d0 = C.L[0][(int64_t)i * W + col] & cons;
+        if (d0 == 0) continue;
+        const bool ok = qn_cone(A, C, S, T, W, col, i, d0, cnt);
+        if (!ok) {
+            if (lane == 0) C.header[0] = 1;
+            break;
+        }
+        u64 orT = 0;
+        for (int q = lane; q < cnt[T]; q += 64) orT |= S.diff(T, q);
+        for (int off = 32; off; off >>= 1) orT |= (u64)__shfl_xor((long long)orT, off);
+        const u64 acc = d0 & ~orT;                           // consensus survives the flip
+        if (acc) {
+            for (int l = 0; l <= T; ++l)
+                for (int q = lane; q < cnt[l]; q += 64) {    // the nodes of a list are distinct: one lane per word
+                    const u64 dq = S.diff(l, q) & acc;
+                    if (dq) C.L[l][(int64_t)S.node(l, q) * W + col] ^= dq;
+                }
+            mine += (long long)((acc >> lane) & 1);
+        }
+        __syncthreads();                                     // the commits land before the next candidate reads them
+    }
+    flipped[col * 64 + lane] = mine;
+}
+
+// list capacities, LDS part and scratch slots from the caps (HOST int64 [T+1])
+static int qn_plan(int T, const int64_t* caps, int lds_entries, QnCone& C) {
+    if (T < 0 || T > QN_MAXT || !caps || lds_entries < 0) return MJX_EINVAL;
+    C.E = lds_entries ? lds_entries : QN_LDS_DEFAULT;
+    if ((size_t)C.E * ((size_t)(T + 1) * 12 + 4) > kQnLdsMax) return MJX_EINVAL;
+    int64_t S = 0;
+    for (int l = 0; l <= T + 1; ++l) {
+        const int64_t cap = (l == 0) ? 1 : caps[l <= T ? l : T];
+        if (cap < 1 || cap > (int64_t)INT32_MAX) return MJX_EINVAL;
+        C.cap[l] = (int)cap;
+        C.soff[l] = (l <= T) ? S : 0;
+        if (l <= T) S += std::max<int64_t>(0, cap - C.E);
+    }
+    for (int l = T + 2; l < QN_MAXT + 2; ++l) { C.cap[l] = 0; C.soff[l] = 0; }
+    C.Sd = S;
+    C.Sc = std::max<int64_t>(0, (int64_t)C.cap[T + 1] - C.E);
+    C.stride = ((C.Sd * 12 + C.Sc * 4 + 7) / 8) * 8;
+    return MJX_OK;
+}
+
+static size_t qn_lds_bytes(int T, int E) { return (size_t)E * ((size_t)(T + 1) * 12 + 4); }
+
+static int64_t qn_header_bytes(int64_t W) { return (1 + 65 * W) * (int64_t)sizeof(u64); }
+
+static int64_t qn_flip_blocks(int64_t n, int64_t W) { return std::min<int64_t>(n * W, kQnMaxBlocks); }
+
+// arguments common to the four entry points; fills C but for the adjacency
+static int qn_setup(int64_t n, int64_t R, int p, int c, uint64_t* const* levels, const int64_t* caps, int lds_entries,
+                    void* scratch, int64_t scratch_bytes, int64_t blocks, QnCone& C) {
+    const int T = p + c - 1;
+    if (p < 0 || c < 0 || T < 0 || T > QN_MAXT || n < 1 || n > (int64_t)INT32_MAX || R < 1 || !levels || !caps ||
+        !scratch)
+        return MJX_EINVAL;
+    if (int rc = qn_plan(T, caps, lds_entries, C)) return rc;
+    const int64_t W = (R + 63) / 64;
+    if (scratch_bytes < qn_header_bytes(W) + blocks * C.stride) return MJX_EINVAL;
+    for (int t = 0; t <= QN_MAXT; ++t) C.L[t] = nullptr;
+    for (int t = 0; t <= T; ++t) {
+        if (!levels[t]) return MJX_EINVAL;
+        C.L[t] = (u64*)levels[t];
+    }
+    C.header = (u64*)scratch;
+    C.lists = (unsigned char*)scratch + qn_header_bytes(W);
+    return MJX_OK;
+}
+
+// header: overflow flag and +1 counts zeroed, counts of L_T, consensus bytes and words
+static int qn_consensus(const QnCone& C, int T, int64_t n, int64_t R, uint8_t* consensus, void* stream) {
+    const int64_t W = (R + 63) / 64;
+    hipStream_t hs = as_stream(stream);
+    MJX_HIP(hipMemsetAsync(C.header, 0, (size_t)(1 + 64 * W) * sizeof(u64), hs), "quench header memset");
+    if (int rc = mjx_popcount_rp((const uint64_t*)C.L[T], n, W, (unsigned long long*)(C.header + 1), stream)) return rc;
+    k_qn_consensus<<<(unsigned)W, 64, 0, hs>>>(C.header + 1, n, R, C.header + 1 + 64 * W, consensus);
+    MJX_LAUNCH_CHECK("k_qn_consensus");
+    return MJX_OK;
+}
+
+template <class Adj>
+static int flip_gain_run(Adj A, int64_t n, int64_t R, int p, int c, const uint64_t* const* levels,
+                         const int64_t* caps, int lds_entries, void* scratch, int64_t scratch_bytes,
+                         uint64_t* removable, uint8_t* consensus, int32_t* gain, void* stream) {
+    if (!removable || !consensus) return MJX_EINVAL;
+    const int64_t W = (R + 63) / 64;
+    if (R < 1 || n < 1 || W > (int64_t)INT32_MAX) return MJX_EINVAL;
+    const int64_t blocks = qn_flip_blocks(n, W);
+    QnCone C;
+    if (int rc = qn_setup(n, R, p, c, (uint64_t* const*)levels, caps, lds_entries, scratch, scratch_bytes, blocks, C))
+        return rc;
+    const int T = p + c - 1;
+    if (int rc = qn_consensus(C, T, n, R, consensus, stream)) return rc;
+    k_flip_gain<Adj><<<(unsigned)blocks, 64, qn_lds_bytes(T, C.E), as_stream(stream)>>>(A, C, T, n, W, R,
+                                                                                      (u64*)removable, gain);
+    MJX_LAUNCH_CHECK("k_flip_gain");
+    return MJX_OK;
+}
+
+template <class Adj>
+static int quench_run(Adj A, int64_t n, int64_t R, int p, int c, uint64_t* const* levels, const int64_t* caps,
+                      int lds_entries, void* scratch, int64_t scratch_bytes, const int32_t* cand,
+                      const int64_t* cand_ptr, uint8_t* consensus, int64_t* flipped, void* stream) {
+    if (!cand_ptr || !consensus || !flipped) return MJX_EINVAL;
+    const int64_t W = (R + 63) / 64;
+    if (R < 1 || n < 1 || W > (int64_t)INT32_MAX) return MJX_EINVAL;
+    QnCone C;
+    if (int rc = qn_setup(n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, W, C)) return rc;
+    const int T = p + c - 1;
+    if (int rc = qn_consensus(C, T, n, R, consensus, stream)) return rc;
+    k_quench<Adj><<<(unsigned)W, 64, qn_lds_bytes(T, C.E), as_stream(stream)>>>(A, C, T, n, W, R, cand, cand_ptr,
+                                                                              (long long*)flipped);
+    MJX_LAUNCH_CHECK("k_quench");
+    return MJX_OK;
+}
+
+}  // namespace mjx
+
+using namespace mjx;
+
+extern "C" int mjx_ell_ball_bound(int64_t n, int d, int T, int64_t* bound_out) {
+    if (!bound_out || n < 1 || d < 0 || T < 0 || T > QN_MAXT) return MJX_EINVAL;
+    int64_t pw = 1, acc = 1;
+    for (int t = 0; t <= T; ++t) {
+        bound_out[t] = std::min<int64_t>(n, acc);
+        pw = (pw > n) ? pw : pw * d;                        // saturating: acc is cut at n anyway
+        acc = std::min<int64_t>(n, acc + pw);
+    }
+    return MJX_OK;
+}
+
+extern "C" int64_t mjx_quench_lds(int T, int lds_entries) {
+    if (T < 0 || T > QN_MAXT || lds_entries < 0) return -1;
+    const size_t b = qn_lds_bytes(T, lds_entries ? lds_entries : QN_LDS_DEFAULT);
+    return b > kQnLdsMax ? -1 : (int64_t)b;
+}
+
+extern "C" int64_t mjx_flip_gain_scratch_bytes(int64_t n, int64_t R, int T, const int64_t* caps, int lds_entries) {
+    QnCone C;
+    if (n < 1 || R < 1 || qn_plan(T, caps, lds_entries, C)) return -1;
+    const int64_t W = (R + 63) / 64;
+    return qn_header_bytes(W) + qn_flip_blocks(n, W) * C.stride;
+}
+
+extern "C" int64_t mjx_quench_scratch_bytes(int64_t R, int T, const int64_t* caps, int lds_entries) {
+    QnCone C;
+    if (R < 1 || qn_plan(T, caps, lds_entries, C)) return -1;
+    const int64_t W = (R + 63) / 64;
+    return qn_header_bytes(W) + W * C.stride;
+}
+
+extern "C" int mjx_flip_gain_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c,
+                                    const uint64_t* const* levels, const int64_t* caps, int lds_entries,
+                                    void* scratch, int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus,
+                                    int32_t* gain, void* stream) {
+    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    return flip_gain_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, removable,
+                         consensus, gain, stream);
+}
+
+extern "C" int mjx_flip_gain_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                                    const uint64_t* const* levels, const int64_t* caps, int lds_entries,
+                                    void* scratch, int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus,
+                                    int32_t* gain, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
+    return flip_gain_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes,
+                         removable, consensus, gain, stream);
+}
+
+extern "C" int mjx_quench_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c,
+                                 uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                                 int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr,
+                                 uint8_t* consensus, int64_t* flipped, void* stream) {
+    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    return quench_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, cand, cand_ptr,
+                      consensus, flipped, stream);
+}
+
+extern "C" int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                                 uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                                 int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr,
+                                 uint8_t* consensus, int64_t* flipped, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;
+    return quench_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, cand,
+                      cand_ptr, consensus, flipped, stream);
+}
