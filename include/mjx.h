@@ -832,6 +832,51 @@ int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int
                       int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr, uint8_t* consensus,
                       int64_t* flipped, void* stream);
 
+/* ---- the quench as independent jobs, state in LDS ------------------------- */
+/*
+ * The same pass (definitions above) for R starts x K restarts: job r*K + k
+ * quenches start r in its own visiting order and, for an ELL stack, on its own
+ * graph.  One workgroup of one wave runs a job with the job's single replica
+ * NODE-packed in LDS (bit v of a bitmap = spin of node v, as mjx_pack_np): the
+ * T+1 levels, a bitmap of marks and the T+2 node lists of the light cone.  The
+ * adjacency is read from global memory.  The pass walks the whole order and
+ * tries every node whose spin is +1; by (3) above the result is the one of the
+ * pass over the initial removable mask.
+ *
+ * LDS of a job: mjx_quench_jobs_lds(n, T, caps) =
+ *   4 * ((T + 2) * 2 * ceil(n/64) + 1 + sum_{t=1..T} min(n, caps[t]) + min(n, caps[T]))
+ * bytes rounded up to 16; -1 when T is outside 0..6, n < 1, a cap < 1, or the
+ * job does not fit 64 KiB (no dynamic-LDS opt-in; n of order 1e5 at T = 3,
+ * d = 4).  DECISION: a shape that does not fit is REFUSED, nothing spills to
+ * caller scratch -- the bitmaps are 9/10 of the budget at the sizes that matter
+ * and cannot spill, and mjx_quench_*_rp remains the path for such a shape.
+ *
+ * s_np: [R][ceil(n/64)] node-packed starts (padding bits ignored).  order:
+ * int32 device array [R or 1][K][n], every row a permutation of 0..n-1;
+ * order_stride_r = K*n, or 0 when the starts share the K orders.  ELL:
+ * graph_stride = n*d for a stack adj[R][n][d] (start r on graph r), 0 for one
+ * shared graph.  CSR: shared graph only.  caps as above; with a stack, of every
+ * graph of it (mjx_ell_ball_bound depends on n and d alone).
+ * Outputs, all on the device: out_np[R*K][ceil(n/64)] with padding bits 0,
+ * flipped[R*K], plus[R*K] (+1 spins of the result), consensus[R] (bytes 0 / 1,
+ * of the start), flag[R*K]: 0, or bit 0 = a list outgrew wrong caps, bit 1 = an
+ * order or adjacency entry outside 0..n-1; such a job stops, writes nothing out
+ * of bounds, and its results are void.  A start without consensus comes back
+ * unchanged with flipped = 0 in each of its K jobs.
+ * MJX_EINVAL: T outside 0..6, n < 1 or n >= 2^31, R < 1, K < 1, R*K >= 2^31, a
+ * NULL pointer, strides other than the above, a shape that does not fit.  No
+ * allocation, no host synchronisation.
+ */
+int64_t mjx_quench_jobs_lds(int64_t n, int T, const int64_t* caps);
+int mjx_quench_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t graph_stride, int64_t R, int64_t K, int p, int c,
+                        const int64_t* caps, const uint64_t* s_np, const int32_t* order, int64_t order_stride_r,
+                        uint64_t* out_np, int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag,
+                        void* stream);
+int mjx_quench_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int64_t K, int p, int c,
+                        const int64_t* caps, const uint64_t* s_np, const int32_t* order, int64_t order_stride_r,
+                        uint64_t* out_np, int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

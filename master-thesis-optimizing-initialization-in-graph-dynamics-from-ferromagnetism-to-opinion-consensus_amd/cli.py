@@ -24,7 +24,11 @@ and write its np.savez keys.
         (quench.quench) of the ``conf`` of an SA / HPR result file (``graphs``:
         one graph per replica, run replica by replica) or an sa-er file
         (``row_ptr``, ``col``: one call); output: the input's arrays plus
-        conf_quenched, mag_quenched, flipped, consensus
+        conf_quenched, mag_quenched, flipped, consensus.  ``--restarts K``
+        (with ``--order-seed``): best of K orders per replica, all (replica,
+        order) jobs in one call (quench.quench_restarts), a graph per replica
+        for ``graphs`` files; the same keys for the best restart plus
+        mag_restarts (R, K) and best
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -95,8 +99,21 @@ def _common(ap):
     ap.add_argument("--out", default=None, help="output .npz (default: the reference's file name)")
 
 
+class _Parser(argparse.ArgumentParser):
+    """Checks that span two options, after the parse."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if a.cmd == "quench":
+            if a.restarts < 0:
+                self.error("--restarts must be >= 0")
+            if a.restarts >= 1 and a.order_seed is None:
+                self.error("--restarts K needs --order-seed: the K orders are drawn from it")
+        return a
+
+
 def build_parser():
-    ap = argparse.ArgumentParser(prog="python -m mjx", description=__doc__.split("\n\n")[0])
+    ap = _Parser(prog="python -m mjx", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
     sa = sub.add_parser("sa", help="code/SA_RRG.py")
     for k, v in SA_DEFAULTS.items():
@@ -150,6 +167,10 @@ def build_parser():
     qu.add_argument("--c", type=int, required=True)
     qu.add_argument("--order-seed", type=int, default=None,
                     help="visit the nodes in np.random.default_rng(S).permutation(n) order (default: 0, 1, ...)")
+    qu.add_argument("--restarts", type=int, default=0,
+                    help="K >= 1: best of K orders per replica in one call (quench.quench_restarts), job (r, k) "
+                         "walking np.random.default_rng([S, r, k]).permutation(n) with S = --order-seed (required); "
+                         "0: one pass as above")
     qu.add_argument("--out", default=None, help="output .npz (default: the input's name + _quenched)")
     return ap
 
@@ -318,10 +339,19 @@ def run_quench(a):
         raise SystemExit(f"{a.inp}: need conf with graphs (sa / hpr files) or with row_ptr, col (sa-er files)")
     conf = np.atleast_2d(res["conf"])
     S = conf.astype(np.int64)                   # the result files hold +-1 as floats
-    if "graphs" in res:
+    if "graphs" in res and res["graphs"].shape[0] != S.shape[0]:
+        raise SystemExit(f"{a.inp}: {res['graphs'].shape[0]} graphs for {S.shape[0]} configurations")
+    if a.restarts >= 1:
+        # best of K orders per replica, every (replica, order) a job of one call; SA / HPR files: the
+        # (R, n, d) stack, a graph per replica
+        from .quench import quench_restarts
+        g = res["graphs"].astype(np.int32) if "graphs" in res else Graph.csr(res["row_ptr"], res["col"])
+        qr = quench_restarts(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed)
+        q = {"conf": qr["conf_best"], "mag": qr["mag_best"], "consensus": qr["consensus"],
+             "flipped": qr["flipped"][np.arange(S.shape[0]), qr["best"]]}      # of the restart that is kept
+        res["mag_restarts"], res["best"] = qr["mag"], qr["best"]
+    elif "graphs" in res:
         # one graph per replica (code/SA_RRG.py:58-62): replica by replica
-        if res["graphs"].shape[0] != S.shape[0]:
-            raise SystemExit(f"{a.inp}: {res['graphs'].shape[0]} graphs for {S.shape[0]} configurations")
         runs = [quench(res["graphs"][k].astype(np.int32), S[k:k + 1], a.p, a.c, seed=a.order_seed)
                 for k in range(S.shape[0])]
         q = {k: np.concatenate([r[k] for r in runs]) for k in ("conf", "mag", "flipped", "consensus")}

@@ -17,8 +17,14 @@ the same evaluator and commits the accepted flips into copies of the levels.
 SA and HPR stop at the first configuration that reaches consensus; this is the
 zero-temperature clean-up after them.
 
-Not covered: an order per replica, a graph per replica inside one call, the
-node-packed layout, several devices.  There is no CPU fallback.
+The local minimum depends on the visiting order.  ``quench_restarts`` runs
+R starts x K orders as R K independent jobs in one call
+(csrc/mjx_quench_lds.hip: a workgroup per job, the job's single replica
+node-packed in LDS), with an order per job and, for an (R, n, d) stack, a graph
+per start, and returns the best of the K results per start.
+
+Not covered: packed input to ``quench_restarts``, a CSR graph per start,
+several devices.  There is no CPU fallback.
 """
 import ctypes
 
@@ -282,4 +288,189 @@ def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, valid
         out["conf"] = conf.to(device=s.device, dtype=s.dtype)
     else:
         out["conf"] = conf.cpu().numpy().astype(np.asarray(s).dtype, copy=False)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# restarts: a job per (start, order), the state in LDS (csrc/mjx_quench_lds.hip)
+# ---------------------------------------------------------------------------
+def restart_order(seed, r, k, n):
+    """The order of job (start r, restart k) under ``seed``."""
+    return np.random.default_rng([int(seed), int(r), int(k)]).permutation(n)
+
+
+def pick_best(sums):
+    """sums: integer (R, K) = sum of the spins of every job's result -> int64
+    [R], per start the restart with the smallest sum, the smallest k on ties."""
+    return np.argmin(np.asarray(sums), axis=1).astype(np.int64)
+
+
+def _check_orders(orders, seed, restarts, R, n):
+    """-> int32 numpy orders (1 or R, K, n); host only."""
+    K = int(restarts)
+    if K < 1:
+        raise ValueError("restarts must be >= 1")
+    if orders is not None and seed is not None:
+        raise ValueError("give orders or seed, not both")
+    if seed is not None:
+        return np.stack([np.stack([restart_order(seed, r, k, n) for k in range(K)])
+                         for r in range(R)]).astype(np.int32)
+    if orders is None:
+        if K != 1:
+            raise ValueError("restarts > 1 needs orders or seed: without them every restart would walk the identity")
+        return np.arange(n, dtype=np.int32).reshape(1, 1, n)
+    o = np.asarray(orders.cpu() if isinstance(orders, torch.Tensor) else orders)
+    if o.ndim not in (1, 2, 3) or o.shape[-1] != n or not np.issubdtype(o.dtype, np.integer):
+        raise ValueError(f"orders must be integer permutations of 0..{n - 1}: (n,), (K, n) or (R, K, n)")
+    o = o.reshape((1,) * (3 - o.ndim) + o.shape).astype(np.int64)
+    if o.shape[1] != K:
+        raise ValueError(f"restarts = {K} but orders holds {o.shape[1]} per start")
+    if o.shape[0] not in (1, R):
+        raise ValueError(f"orders of shape (R, K, n) need R = {R} starts, got {o.shape[0]}")
+    rows = o.reshape(-1, n)
+    if o.size and (o.min() < 0 or o.max() >= n or
+                   np.bincount((rows + n * np.arange(rows.shape[0])[:, None]).ravel(), minlength=rows.size).max() != 1):
+        raise ValueError(f"every row of orders must be a permutation of 0..{n - 1}")
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
+def _host_shapes(graph, s):
+    """(graph per start?, n, R, ndim of s) without touching the device."""
+    if isinstance(graph, Graph):
+        stack, n = False, graph.n
+    elif isinstance(graph, (list, tuple)) and any(isinstance(x, Graph) for x in graph):
+        raise ValueError("a graph per start must be an (R, n, d) neighbour stack (ELL); a CSR graph is shared by "
+                         "all starts")
+    else:
+        gs = tuple(graph.shape) if hasattr(graph, "shape") else np.shape(graph)
+        if len(gs) not in (2, 3):
+            raise ValueError("graph must be a Graph, an (n, d) neighbour array or an (R, n, d) stack of them")
+        stack, n = len(gs) == 3, int(gs[-2])
+    ss = tuple(s.shape) if hasattr(s, "shape") else np.shape(s)
+    if len(ss) not in (1, 2) or ss[-1] != n:
+        raise ValueError(f"spins must be (n,) or (R, n) with n = {n}; packed input is not taken here")
+    R = 1 if len(ss) == 1 else int(ss[0])
+    if R < 1:
+        raise ValueError("no starts")
+    if stack and int(gs[0]) != R:
+        raise ValueError(f"a graph per start: {int(gs[0])} graphs for {R} starts")
+    return stack, n, R, len(ss)
+
+
+def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t):
+    """The device call: R x K jobs -> (out_np int64 (R K, ceil(n/64)), flipped int64 [R K], plus int64 [R K],
+    consensus uint8 [R]).  g: the shared graph, or any graph of ``adj_stack`` (device int32 (R, n, d): a graph
+    per start); s_np int64 (R, ceil(n/64)); order_t device int32 (1 or R, K, n)."""
+    n, dev, st = g.n, s_np.device, _device.stream_handle()
+    Wn = (n + 63) // 64
+    out_np = torch.empty((R * K, Wn), dtype=torch.int64, device=dev)
+    flipped = torch.empty(R * K, dtype=torch.int64, device=dev)
+    plus = torch.empty(R * K, dtype=torch.int64, device=dev)
+    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
+    flag = torch.empty(R * K, dtype=torch.int32, device=dev)
+    tail = (R, K, p, c, caps, _device.ptr(s_np), _device.ptr(order_t), K * n if order_t.shape[0] > 1 else 0,
+            _device.ptr(out_np), _device.ptr(flipped), _device.ptr(plus), _device.ptr(consensus), _device.ptr(flag), st)
+    if g.kind == "ell":
+        adj = g.adj if adj_stack is None else adj_stack
+        _lib.call("mjx_quench_jobs_ell", _device.ptr(adj) if g.d else None, n, g.d,
+                  0 if adj_stack is None else n * g.d, *tail)
+    else:
+        _lib.call("mjx_quench_jobs_csr", _device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n, *tail)
+    flags = int(flag.max().item())
+    if flags & 1:
+        raise _lib.MjxError("quench_restarts: a light-cone list outgrew the ball bound of the graph")
+    if flags:
+        raise _lib.MjxError("quench_restarts: an order or adjacency entry lies outside 0..n-1")
+    return out_np, flipped, plus, consensus
+
+
+def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all=False, kernel=None, validate=True):
+    """Best of ``restarts`` greedy passes per start, every (start r, restart k)
+    a job with its own visiting order, all jobs in one device call.
+
+    graph: as for ``quench``, shared by the starts; or an (R, n, d) integer
+    array, start r living on graph r (ELL only).  s: +-1 spins (n,) or (R, n).
+    orders: (n,), (K, n) shared by the starts, or (R, K, n), every row a
+    permutation of 0..n-1 and K = ``restarts``; or ``seed``: job (r, k) walks
+    ``np.random.default_rng([seed, r, k]).permutation(n)`` (``restart_order``).
+    With neither, ``restarts`` must be 1 and the order is the identity.  A
+    job's result is ``quench``'s for that start, graph and order.  A shape whose
+    job does not fit the workgroup's LDS raises ValueError: ``quench`` is the
+    path for it.
+
+    Returns a dict: ``mag`` float64 (R, K), ``flipped`` int64 (R, K),
+    ``consensus`` bool [R] (of the input), ``best`` int64 [R] (the k with the
+    smallest sum of spins, the smallest k on ties), ``conf_best`` (shape, kind
+    and dtype of the input), ``mag_best`` float64 [R], ``state_best`` (device
+    tensor int64 (R, ceil(n/64)): node-packed ``conf_best``, padding bits 0)
+    and, with ``keep_all``, ``conf`` int8 (R, K, n).  numpy in -> numpy out,
+    tensor in -> tensors on the input's device.  The input is never written;
+    starts without consensus come back unchanged in every restart."""
+    p, c, T = _steps(p, c)
+    if kernel:
+        raise ValueError(f"unknown kernel options {sorted(dict(kernel))}")
+    stack, n, R, ndim = _host_shapes(graph, s)
+    K = int(restarts)
+    orders = _check_orders(orders, seed, K, R, n)
+    if stack:
+        adj = graph.cpu().numpy() if isinstance(graph, torch.Tensor) else np.asarray(graph)
+        if not np.issubdtype(adj.dtype, np.integer):
+            raise ValueError("the (R, n, d) graph stack must be an integer array")
+        if adj.size and (adj.min() < 0 or adj.max() >= n):
+            raise ValueError("adjacency index out of range")
+        d = int(adj.shape[2])
+        adj_t = _device.to_device(adj.astype(np.int32, copy=False))
+        graphs = [Graph("ell", n, d=d, adj=adj_t[r]) for r in range(R)]
+        g = graphs[0]
+    else:
+        g = as_graph(graph)
+        graphs = [g]
+    if validate:
+        for gr in graphs:
+            _check_symmetric(gr)
+    caps = _caps(g, T)                      # ELL: a function of (n, d) alone, the same for every graph of a stack
+    lib = _lib.load()
+    lds = int(lib.mjx_quench_jobs_lds(n, T, caps))
+    if lds < 0:
+        raise ValueError(f"quench_restarts: a job of n = {n}, p + c - 1 = {T} (ball bound {list(caps)}) does not fit "
+                         "the workgroup's LDS; quench is the path for this shape")
+    t = _device.to_device(s)
+    if t.dim() == 1:
+        t = t[None, :]
+    if t.dtype not in (torch.int8, torch.int32, torch.int64):
+        t = t.to(torch.int64)
+    t = t.contiguous()
+    dev, st, Wn = t.device, _device.stream_handle(), (n + 63) // 64
+    s_np = torch.empty((R, Wn), dtype=torch.int64, device=dev)
+    code, step = _device.dtype_code(t), n * t.element_size()
+    for r in range(R):
+        _lib.call("mjx_pack_np", t.data_ptr() + r * step, code, n, s_np.data_ptr() + r * Wn * 8, st)
+    order_t = _device.to_device(orders)
+    out_np, flipped, plus, consensus = _run_jobs(g, adj_t if stack else None, R, K, p, c, caps, s_np, order_t)
+    sums = 2 * plus.cpu().numpy().reshape(R, K) - n
+    best = pick_best(sums)
+    # sum(s) / n as numpy divides two integers, as quench does
+    mag = sums / n
+    mag_best = mag[np.arange(R), best]
+    state_best = out_np.view(R, K, Wn)[torch.arange(R, device=dev), torch.from_numpy(best).to(dev)].contiguous()
+
+    def rows(bits, dtype):
+        conf = torch.empty((bits.shape[0], n), dtype=dtype, device=dev)
+        dc, row = _device.dtype_code(conf), n * conf.element_size()
+        for j in range(bits.shape[0]):
+            _lib.call("mjx_unpack_np", bits.data_ptr() + j * Wn * 8, n, conf.data_ptr() + j * row, dc, st)
+        return conf
+
+    conf_best = rows(state_best, t.dtype)
+    if ndim == 1:
+        conf_best = conf_best[0]
+    if isinstance(s, torch.Tensor):
+        conf_best = conf_best.to(device=s.device, dtype=s.dtype)
+    else:
+        conf_best = conf_best.cpu().numpy().astype(np.asarray(s).dtype, copy=False)
+    out = {"mag": _like(torch.from_numpy(mag), s), "flipped": _like(flipped.view(R, K), s),
+           "consensus": _like(consensus.to(torch.bool), s), "best": _like(torch.from_numpy(best), s),
+           "conf_best": conf_best, "mag_best": _like(torch.from_numpy(mag_best), s), "state_best": state_best}
+    if keep_all:
+        out["conf"] = _like(rows(out_np, torch.int8).view(R, K, n), s)
     return out
