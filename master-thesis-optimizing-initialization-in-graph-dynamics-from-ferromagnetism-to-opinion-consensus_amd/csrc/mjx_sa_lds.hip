@@ -39,7 +39,7 @@
 // as every other SA mode.
 #include "mjx_common.h"
 #include <type_traits>
-#include "mjx_mt.h"
+#include "mjx_sa_core.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -120,6 +120,310 @@ __device__ unsigned long long mjx_sa_lds_prof[32];
 #define LDS_STAMP(k) do {} while (0)
 #endif
 
+// ---------------------------------------------------------------------------
+// What every kernel of this unit does the same way: rows and the majority
+// rule, the launch's setup, the replica's loop state, the numpy-exact parse of
+// the MT19937 stream, the Metropolis test, the trace and the write-back.  The
+// kernels below differ in how a proposal's light cone is evaluated.
+//
+// k_sa_lds and k_sa_lds_cu are built from these helpers.  k_sa_lds_fast, _pair,
+// _multi, _wg and _wg1 KEEP THEIR OWN TEXT of the same steps (rows / majority
+// closures, setup, state load with the randint mask and the "+v" pin, parser
+// or ring, the screened accept test, write-back; _fast and _wg call the trace
+// helpers): through the helpers each of them measured slower than before or
+// lost a wave per SIMD, and only the whole own text gives the former code
+// ("The LDS kernels' shared parts").  A fix to scan_window,
+// draw_crossing, window_starts, Ring, load_state, sa_accept_screened or
+// write_back_level0 has to be repeated in those five kernels.
+
+// neighbours of v from its row of four uint16 (d <= 4): one 8-byte read
+template <int D>
+__device__ __forceinline__ void unpack_row(uint2 x, int (&o)[D]) {
+    o[0] = (int)(x.x & 0xffffu);
+    if constexpr (D > 1) o[1] = (int)(x.x >> 16);
+    if constexpr (D > 2) o[2] = (int)(x.y & 0xffffu);
+    if constexpr (D > 3) o[3] = (int)(x.y >> 16);
+}
+template <int D>
+__device__ __forceinline__ void unpack_row(const uint16_t* rows, int v, int (&o)[D]) {
+    unpack_row<D>(*reinterpret_cast<const uint2*>(rows + v * 4), o);
+}
+
+// always-stay majority (code/SA_RRG.py:19-20)
+__device__ __forceinline__ uint32_t maj_of(int d, int ones, uint32_t own) {
+    return (2 * ones > d) ? 1u : ((2 * ones < d) ? 0u : own);
+}
+template <int D>
+__device__ __forceinline__ uint32_t maj(int ones, uint32_t own) {
+    return maj_of(D, ones, own);
+}
+
+// ---- launch setup, by threads tid, tid + nt, ... (nt = 64 in the one-wave
+// kernels, the workgroup in the whole-CU ones)
+
+// the adjacency rows of graph g into LDS: d entries in a row of rw uint16
+__device__ __forceinline__ void stage_rows(uint16_t* rows, const int32_t* g, int64_t n, int d, int rw, int tid, int nt) {
+    for (int64_t q = tid; q < n * d; q += nt) {
+        const int64_t v = q / d;
+        rows[v * rw + (q - v * d)] = (uint16_t)g[q];
+    }
+}
+
+// a 624-word MT19937 state, into LDS at launch start and back at its end
+__device__ __forceinline__ void copy_mt(uint32_t* dst, const uint32_t* src, int tid, int nt) {
+    for (int k = tid; k < MT_N; k += nt) dst[k] = src[k];
+}
+
+// level 0 of replica r from the replica-packed s by ballots: word w to
+// lev[LVS * w] (LVS: the uint32 per level word entry, 1 for a plain bit array)
+// and to lev0s[w], the copy the write-back compares with.  A wave takes the 64
+// nodes from v_first, then every v_stride-th 64.
+template <int LVS>
+__device__ __forceinline__ void level0_from_s(uint32_t* lev, uint32_t* lev0s, const u64* s, int64_t n, int64_t W,
+                                              int64_t r, int nw, int lane, int64_t v_first, int v_stride) {
+    const int64_t col = r >> 6;
+    const u64 rbit = 1ull << (r & 63);
+    for (int64_t v0 = v_first; v0 < (int64_t)nw * 32; v0 += v_stride) {
+        const int64_t v = v0 + lane;
+        const bool b = v < n && (s[v * W + col] & rbit);
+        const u64 m = __ballot(b);
+        if (lane < 2) {
+            const uint32_t x = (uint32_t)(m >> (32 * lane));
+            lev[LVS * ((v0 >> 5) + lane)] = x;
+            lev0s[(v0 >> 5) + lane] = x;
+        }
+    }
+}
+
+// the launch's changes of level 0 back to s: the replica's bit of the changed
+// nodes by atomicXor (the other 63 replicas of a word are other workgroups)
+template <int LVS>
+__device__ __forceinline__ void write_back_level0(const uint32_t* lev, const uint32_t* lev0s, u64* s, int64_t n,
+                                                  int64_t W, int64_t r, int tid, int nt) {
+    for (int64_t v = tid; v < n; v += nt) {
+        if (((lev[LVS * (v >> 5)] ^ lev0s[v >> 5]) >> (v & 31)) & 1u)
+            atomicXor((unsigned long long*)&s[v * W + (r >> 6)], 1ull << (r & 63));
+    }
+}
+
+// ---- the replica's loop state (code/SA_RRG.py:66-72) and what its draws
+// need: randint(0, n)'s range n - 1 and bit mask (numpy's masked rejection),
+// 1 / n (screening only: dE itself divides).  With PIN (every kernel but the
+// serial k_sa_lds) the float64 schedule lives in VGPRs (its arithmetic is
+// vector anyway): the scalar file is what the step's control flow needs.
+// (Copies of the mask build and the pin: k_sa_lds_fast, _pair, _multi, _wg, _wg1.)
+template <bool PIN = true>
+__device__ __forceinline__ void load_state(const mjx_sa_state& st, int64_t r, int64_t n, double& a, double& b,
+                                           int64_t& t, int64_t& sum_end, int& done, int& idx, uint32_t& rng,
+                                           uint32_t& mask, double& inv_n, double& par_a, double& par_b,
+                                           double& a_cap, double& b_cap) {
+    a = st.a[r];
+    b = st.b[r];
+    t = st.t[r];
+    sum_end = st.sum_end[r];
+    done = st.done[r];
+    idx = st.mt_idx[r];
+    rng = (uint32_t)(n - 1);
+    mask = rng;
+    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+    inv_n = 1.0 / (double)n;
+    if constexpr (PIN) {
+        asm volatile("" : "+v"(a), "+v"(b), "+v"(par_a), "+v"(par_b), "+v"(a_cap), "+v"(b_cap), "+v"(inv_n));
+    }
+}
+
+// its counterpart, by one lane (the stream position is each kernel's own)
+__device__ __forceinline__ void store_state(double* st_a, double* st_b, int64_t* st_t, int64_t* st_sum,
+                                            int32_t* st_done, int32_t* st_tie, int64_t r, double a, double b,
+                                            int64_t t, int64_t sum_end, int done, int ties) {
+    st_a[r] = a;
+    st_b[r] = b;
+    st_t[r] = t;
+    st_sum[r] = sum_end;
+    st_done[r] = done;
+    if (st_tie) st_tie[r] += ties;
+}
+
+// ---- the stream (code/SA_RRG.py:73,76): randint(0, n) is numpy's masked
+// rejection over tempered words, rand() the two words after the accepted one
+// (copies of the window scan and the crossing draw: the parsers of
+// k_sa_lds_fast, _pair, _multi, _wg, _wg1)
+
+// up to 64 words at idx, one per lane: tempered (tw), masked (y), and the
+// ballot of the ones randint accepts; lim words are left in the state
+struct Window {
+    int lim;
+    uint32_t tw, y;
+    bool ok;
+    u64 okm;
+};
+__device__ __forceinline__ Window scan_window(const uint32_t* mt, int idx, int lane, uint32_t mask, uint32_t rng) {
+    Window wd;
+    wd.lim = (MT_N - idx < 64) ? MT_N - idx : 64;
+    wd.tw = 0;
+    wd.y = 0;
+    wd.ok = false;
+    if (lane < wd.lim) {
+        wd.tw = mt_temper(mt[idx + lane]);
+        wd.y = wd.tw & mask;
+        wd.ok = wd.y <= rng;
+    }
+    wd.okm = __ballot(wd.ok);
+    return wd;
+}
+
+// rand()'s two words drawn serially from idx, just after i's word: `twist`
+// (which leaves idx = 0) runs where the state ends, between any two of the
+// three words, as numpy does
+template <class Twist>
+__device__ __forceinline__ void draw_crossing(const uint32_t* mt, int& idx, uint32_t& w1, uint32_t& w2, Twist&& twist) {
+    if (idx >= MT_N) twist();
+    w1 = mt_temper(mt[idx]);
+    idx += 1;
+    if (idx >= MT_N) twist();
+    w2 = mt_temper(mt[idx]);
+    idx += 1;
+}
+
+// The proposal ring of the whole-CU kernel k_sa_lds_cu (k_sa_lds_wg keeps a
+// copy of the same ring in its own text: twist, twist_ok, parse_window, room),
+// filled by the parse wave: slot q & 63 holds proposal q of the launch (i, u, end: the
+// MT index after its draws, bit 10 its state generation's parity).  npend
+// proposals parsed, pk taken (running counts, every wave tracks pk); the parse
+// wave appends while the round evaluates, into slots the round does not read,
+// and keeps slot pk-1 (the last taken proposal's end) for the launch's MT
+// position.  A twist under unconsumed proposals first saves the old state to
+// mt_out (the replica's st.mt): the launch ends on either generation (the
+// buffer the last taken proposal drew from).  The counts, the stream index
+// and the generation are the kernel's own variables (the rounds use them).
+struct Ring {
+    int* q_i;
+    int* q_end;
+    double* q_u;
+    uint32_t* mt;
+    uint32_t* mt_out;
+    uint32_t rng, mask;
+    int lane;
+    int& idx;
+    int& gen;
+    uint32_t& npend;
+    uint32_t& pk;
+};
+__device__ __forceinline__ void ring_twist(const Ring& rg) {
+    copy_mt(rg.mt_out, rg.mt, rg.lane, 64);
+    lds_twist(rg.mt, rg.lane);
+    rg.idx = 0;
+    rg.gen ^= 1;
+}
+// A twist is refused while the last taken proposal (slot pk-1, kept for the
+// launch's end) still draws from the previous generation: mt_out holds one
+// old generation only, so the end's generation is never more than one
+// behind and bit 10's parity names it.  (With nothing pending -- 624 words
+// parsed without one acceptable proposal, never in practice -- the twist
+// goes ahead rather than stall.)
+__device__ __forceinline__ bool ring_twist_ok(const Ring& rg) {
+    const int lg = (rg.pk > 0u) ? ((rg.q_end[(rg.pk - 1u) & 63u] >> 10) & 1) : 0;
+    return lg == rg.gen || rg.npend == rg.pk;
+}
+__device__ __forceinline__ uint32_t ring_room(const Ring& rg) { return 63u - (rg.npend - rg.pk); }     // slot pk-1 kept
+// the proposal starts of a window (each: the first acceptable word at or after
+// the previous end, then rand()'s two words) whose words fit it, at most `room`
+__device__ __forceinline__ u64 window_starts(const Window& wd, uint32_t room) {
+    u64 stm = mt_window_starts(wd.ok) & ((wd.lim >= 2) ? ((1ull << (wd.lim - 2)) - 1ull) : 0ull);
+    while ((uint32_t)__popcll(stm) > room) stm &= ~(1ull << (63 - __clzll(stm)));
+    return stm;
+}
+// one window of up to 64 words at idx: at most `room` proposals appended,
+// each(slot, i) called by the appending lane for every one; false when a
+// refused twist leaves it for after the round
+template <class Each>
+__device__ __forceinline__ bool ring_parse_window(const Ring& rg, uint32_t room, Each&& each) {
+    if (rg.idx >= MT_N) {
+        if (!ring_twist_ok(rg)) return false;
+        ring_twist(rg);
+    }
+    const Window wd = scan_window(rg.mt, rg.idx, rg.lane, rg.mask, rg.rng);
+    const u64 stm = window_starts(wd, room);
+    const uint32_t got = (uint32_t)__popcll(stm);
+    if (got > 0) {
+        const uint32_t x1 = mt_next_lane(wd.tw);
+        const uint32_t x2 = mt_next_lane(x1);
+        if ((stm >> rg.lane) & 1ull) {
+            const int q = (int)((rg.npend + (uint32_t)__popcll(stm & ((1ull << rg.lane) - 1ull))) & 63u);
+            rg.q_i[q] = (int)wd.y;
+            rg.q_u[q] = mt_double(x1, x2);
+            rg.q_end[q] = (rg.idx + rg.lane + 3) | (rg.gen << 10);
+            each(q, (int)wd.y);
+        }
+        rg.npend += got;
+        rg.idx += 66 - __clzll(stm);                         // after the last start's two words
+        return true;
+    }
+    if (room == 0) return true;
+    if (!wd.okm) { rg.idx += wd.lim; return true; }
+    const int f = __ffsll((unsigned long long)wd.okm) - 1;
+    if (f > 0) { rg.idx += f; return true; }
+    if (rg.idx + 2 >= MT_N && !ring_twist_ok(rg)) return false;
+    // i is the window's first word and rand()'s two words cross the end of the state
+    const int iv = __builtin_amdgcn_readlane((int)wd.y, 0);
+    uint32_t w1, w2;
+    rg.idx += 1;
+    draw_crossing(rg.mt, rg.idx, w1, w2, [&]() { ring_twist(rg); });
+    if (rg.lane == 0) {
+        const int q = (int)(rg.npend & 63u);
+        rg.q_i[q] = iv;
+        rg.q_u[q] = mt_double(w1, w2);
+        rg.q_end[q] = rg.idx | (rg.gen << 10);
+        each(q, iv);
+    }
+    rg.npend += 1;
+    return true;
+}
+
+// ---- u < min(1, exp(-dE)), dE = num / n (code/SA_RRG.py:75-76), decided by an
+// fp32 exp wherever u is farther from it than that exp's error (|x| * 2^-24
+// from rounding x, a few ulp from the exp itself: 1e-6 (1 + |x|) relative
+// covers both); otherwise, and when the trace wants it (want_dE), the float64
+// dE and exp of the reference, unchanged.  Same decision bit for bit.  `tie`:
+// a float64 decision with u within 4 ulp of exp(-dE) (counted in tr_tie).
+// (Copies of this test: k_sa_lds_fast, _pair, _multi, _wg, _wg1.)
+__device__ __forceinline__ bool sa_accept_screened(double num, double inv_n, int64_t n, double u, bool want_dE,
+                                                   double& dE, bool& tie) {
+    dE = 0.0;
+    tie = false;
+    const float xf = (float)(-num * inv_n);
+    const float ef = __expf(xf);
+    const float mg = ef * (1e-6f * (1.0f + fabsf(xf))) + 1e-37f;
+    if (fabs(u - (double)ef) > (double)mg) {
+        if (want_dE) dE = num / (double)n;
+        return u < (double)ef;
+    }
+    dE = num / (double)n;
+    const double e = exp(-dE);
+    const double prob = (e < 1.0) ? e : 1.0;                    // (code/SA_RRG.py:75)
+    tie = e < 1.0 && fabs(u - e) <= 4.0 * (nextafter(e, 2.0) - e);
+    return u < prob;                                            // (code/SA_RRG.py:76)
+}
+
+// ---- the trace: a step's row at `at` = k * R + r, and the rows of the steps
+// of this launch after the replica finished
+__device__ __forceinline__ void trace_step(const mjx_sa_state& st, int64_t at, int iv, bool acc, int64_t sum_end,
+                                           double dE) {
+    if (st.tr_i) st.tr_i[at] = iv;
+    if (st.tr_acc) st.tr_acc[at] = acc ? 1 : 0;
+    if (st.tr_sum) st.tr_sum[at] = sum_end;
+    if (st.tr_dE) st.tr_dE[at] = dE;
+}
+__device__ __forceinline__ void trace_tail(const mjx_sa_state& st, int64_t k, int64_t nsteps, int64_t R, int64_t r,
+                                           int64_t sum_end) {
+    for (; k < nsteps; ++k) {
+        if (st.tr_i) st.tr_i[k * R + r] = -1;
+        if (st.tr_acc) st.tr_acc[k * R + r] = -1;
+        if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
+        if (st.tr_dE) st.tr_dE[k * R + r] = 0.0;
+    }
+}
+
 // Level t of the replica is a bit array (bit v = the cached value onestep^t(s)
 // of node v) interleaved word by word with a change-bit array: lv[2(t nw + w)]
 // = level word w, lv[2(t nw + w) + 1] = change word w.  During a proposal the
@@ -138,8 +442,6 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
     const int d = (D > 0) ? D : dd;
     const int lane = threadIdx.x;
     const int64_t r = blockIdx.x;
-    const int64_t col = r >> 6;
-    const u64 rbit = 1ull << (r & 63);
     const int nw = geo.nw, rw = geo.rw, lc = geo.lc;
     uint16_t* rows = reinterpret_cast<uint16_t*>(smem);
     uint32_t* lv = reinterpret_cast<uint32_t*>(smem + geo.off_lev);       // {level, change} word pairs
@@ -155,50 +457,31 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
         const uint2 x = *reinterpret_cast<const uint2*>(lv + 2 * (t * nw + (v >> 5)));
         return ((x.x ^ x.y) >> (v & 31)) & 1u;
     };
-    // neighbours of v: one 8-byte read for d <= 4
-    auto nbrs = [&](int v, int (&o)[D > 0 ? D : 16]) {
+    // neighbours of v: the runtime-degree row (d > 4, or D = 0) entry by entry
+    auto row_of = [&](int v, int (&o)[D > 0 ? D : 16]) {
         if constexpr (D > 0 && D <= 4) {
-            const uint2 x = *reinterpret_cast<const uint2*>(rows + v * 4);
-            o[0] = (int)(x.x & 0xffffu);
-            if constexpr (D > 1) o[1] = (int)(x.x >> 16);
-            if constexpr (D > 2) o[2] = (int)(x.y & 0xffffu);
-            if constexpr (D > 3) o[3] = (int)(x.y >> 16);
+            unpack_row<D>(rows, v, o);
         } else {
             for (int q = 0; q < d; ++q) o[q] = rows[v * rw + q];
         }
     };
 
     // ---- launch setup: rows, level 0, MT state; then levels 1..T by sweeps in LDS
-    for (int64_t q = lane; q < n * d; q += 64) {
-        const int64_t v = q / d;
-        rows[v * rw + (q - v * d)] = (uint16_t)g[q];
-    }
-    for (int64_t v0 = 0; v0 < (int64_t)nw * 32; v0 += 64) {
-        const int64_t v = v0 + lane;
-        const bool b = v < n && (s[v * W + col] & rbit);
-        const u64 m = __ballot(b);
-        if (lane < 2) {
-            const uint32_t x = (uint32_t)(m >> (32 * lane));
-            lword(0, (int)(v0 >> 5) + lane) = x;
-            lev0s[(v0 >> 5) + lane] = x;
-        }
-    }
+    stage_rows(rows, g, n, d, rw, lane, 64);
+    level0_from_s<2>(lv, lev0s, s, n, W, r, nw, lane, 0, 64);
     for (int k = lane; k < (T + 1) * nw; k += 64) lv[2 * k + 1] = 0u;
-    for (int k = lane; k < MT_N; k += 64) mt[k] = st.mt[r * MT_N + k];
+    copy_mt(mt, st.mt + r * MT_N, lane, 64);
     wave_sync();
-    auto maj = [&](int ones, uint32_t own) -> uint32_t {       // always-stay majority (code/SA_RRG.py:19-20)
-        return (2 * ones > d) ? 1u : ((2 * ones < d) ? 0u : own);
-    };
     for (int t = 1; t <= T; ++t) {
         for (int64_t v0 = 0; v0 < (int64_t)nw * 32; v0 += 64) {
             const int v = (int)(v0 + lane);
             uint32_t nb = 0;
             if (v < n) {
                 int nv[D > 0 ? D : 16];
-                nbrs(v, nv);
+                row_of(v, nv);
                 int ones = 0;
                 for (int q = 0; q < d; ++q) ones += (int)seen(t - 1, nv[q]);
-                nb = maj(ones, seen(t - 1, v));
+                nb = maj_of(d, ones, seen(t - 1, v));
             }
             const u64 m = __ballot(nb != 0);
             if (lane < 2) lword(t, (int)(v0 >> 5) + lane) = (uint32_t)(m >> (32 * lane));
@@ -207,37 +490,28 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
     }
 
     // ---- the steps
-    double a = st.a[r], b = st.b[r];
-    int64_t t = st.t[r], sum_end = st.sum_end[r];
-    int done = st.done[r];
-    int idx = st.mt_idx[r];
-    int ties = 0;
-    const uint32_t rng = (uint32_t)(n - 1);
-    uint32_t mask = rng;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+    double a, b, inv_n;
+    int64_t t, sum_end;
+    int done, idx, ties = 0;
+    uint32_t rng, mask;
+    load_state<false>(st, r, n, a, b, t, sum_end, done, idx, rng, mask, inv_n, par_a, par_b, a_cap, b_cap);
+    auto twist = [&]() {
+        lds_twist(mt, lane);
+        idx = 0;
+    };
     int64_t k = 0;
     for (; k < nsteps && done == 0; ++k) {
         // randint(low=0, high=n) (code/SA_RRG.py:73): numpy's masked rejection, 64 words per ballot
         int iv = -1;
         while (iv < 0) {
-            if (idx >= MT_N) {
-                lds_twist(mt, lane);
-                idx = 0;
-            }
-            const int q = idx + lane;
-            uint32_t y = 0;
-            bool ok = false;
-            if (q < MT_N) {
-                y = mt_temper(mt[q]) & mask;
-                ok = y <= rng;
-            }
-            const u64 bal = __ballot(ok);
-            if (bal) {
-                const int f = __ffsll((unsigned long long)bal) - 1;
-                iv = __shfl((int)y, f, 64);
+            if (idx >= MT_N) twist();
+            const Window wd = scan_window(mt, idx, lane, mask, rng);
+            if (wd.okm) {
+                const int f = __ffsll((unsigned long long)wd.okm) - 1;
+                iv = __shfl((int)wd.y, f, 64);
                 idx += f + 1;
             } else {
-                idx += (MT_N - idx < 64) ? MT_N - idx : 64;
+                idx += wd.lim;
             }
         }
         // rand() (code/SA_RRG.py:76): two consecutive words, one read when no twist falls between
@@ -247,10 +521,7 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
             w2 = mt_temper(mt[idx + 1]);
             idx += 2;
         } else {
-            if (idx >= MT_N) { lds_twist(mt, lane); idx = 0; }
-            w1 = mt_temper(mt[idx++]);
-            if (idx >= MT_N) { lds_twist(mt, lane); idx = 0; }
-            w2 = mt_temper(mt[idx++]);
+            draw_crossing(mt, idx, w1, w2, twist);
         }
         const double u = mt_double(w1, w2);
         // level 0: C_0 = {i}
@@ -277,10 +548,10 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
                     const int v = (int)prev[slot];
                     cand = (j == 0) ? v : (int)rows[v * rw + j - 1];
                     int nv[D > 0 ? D : 16];
-                    nbrs(cand, nv);
+                    row_of(cand, nv);
                     int ones = 0;
                     for (int e = 0; e < d; ++e) ones += (int)seen(l - 1, nv[e]);
-                    const uint32_t nb = maj(ones, seen(l - 1, cand));
+                    const uint32_t nb = maj_of(d, ones, seen(l - 1, cand));
                     const uint32_t bit = 1u << (cand & 31);
                     if (nb != ((lword(l, cand >> 5) >> (cand & 31)) & 1u)) {
                         // first mark of cand at level l (candidates repeat)
@@ -307,15 +578,10 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
             ds = wave_sum(ds);
         }
         const int64_t sum_new = sum_end + ds;
-        // delta_H (code/SA_RRG.py:37), same operation order, no contraction
-        const double si = old_i ? 1.0 : -1.0;
-        const double t1 = (-2.0 * a) * si;
-        const double t2 = b * (double)(sum_end - sum_new);
-        const double dE = (t1 + t2) / (double)n;
-        const double e = exp(-dE);
-        const double prob = (e < 1.0) ? e : 1.0;                    // (code/SA_RRG.py:75)
-        const bool acc = u < prob;                                  // (code/SA_RRG.py:76)
-        if (e < 1.0 && fabs(u - e) <= 4.0 * (nextafter(e, 2.0) - e)) ++ties;
+        // delta_H and the unscreened float64 test (code/SA_RRG.py:37,75-76)
+        const SaVerdict vd = sa_metropolis(a, b, old_i ? 1.0 : -1.0, sum_end, sum_new, n, u);
+        const bool acc = vd.acc;
+        if (vd.tie) ++ties;
         // accepted (code/SA_RRG.py:77): marked bits into the levels; always: clear the marks
         for (int l = 0; l <= last; ++l) {
             const uint32_t* cl = lst + l * lc;
@@ -332,38 +598,17 @@ __global__ void __launch_bounds__(64) k_sa_lds(const int32_t* __restrict__ adj, 
         t += 1;                                                     // (code/SA_RRG.py:82)
         if (t > t_cap) done = 2;                                    // (code/SA_RRG.py:84)
         else if (sum_end == n) done = 1;                            // m(s_endstate(s)) == 1
-        if (lane == 0) {
-            if (st.tr_i) st.tr_i[k * R + r] = iv;
-            if (st.tr_acc) st.tr_acc[k * R + r] = acc ? 1 : 0;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = dE;
-        }
+        if (lane == 0) trace_step(st, k * R + r, iv, acc, sum_end, vd.dE);
         wave_sync();
     }
-    // steps of this launch after the replica finished
-    if (lane == 0) {
-        for (; k < nsteps; ++k) {
-            if (st.tr_i) st.tr_i[k * R + r] = -1;
-            if (st.tr_acc) st.tr_acc[k * R + r] = -1;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = 0.0;
-        }
-    }
-    // ---- write back: changed configuration bits, the stream, the replica state
-    for (int64_t v0 = 0; v0 < n; v0 += 64) {
-        const int v = (int)(v0 + lane);
-        if (v < n && (((lword(0, v >> 5) ^ lev0s[v >> 5]) >> (v & 31)) & 1u))
-            atomicXor((unsigned long long*)&s[(int64_t)v * W + col], (unsigned long long)rbit);
-    }
-    for (int q = lane; q < MT_N; q += 64) st.mt[r * MT_N + q] = mt[q];
+    if (lane == 0) trace_tail(st, k, nsteps, R, r, sum_end);
+    // ---- write back: changed configuration bits, the stream (no draw-ahead:
+    // idx is numpy's), the replica state
+    write_back_level0<2>(lv, lev0s, s, n, W, r, lane, 64);
+    copy_mt(st.mt + r * MT_N, mt, lane, 64);
     if (lane == 0) {
         st.mt_idx[r] = idx;
-        st.a[r] = a;
-        st.b[r] = b;
-        st.t[r] = t;
-        st.sum_end[r] = sum_end;
-        st.done[r] = done;
-        if (st.tr_tie) st.tr_tie[r] += ties;
+        store_state(st.a, st.b, st.t, st.sum_end, st.done, st.tr_tie, r, a, b, t, sum_end, done, ties);
     }
 }
 
@@ -417,6 +662,11 @@ __global__ void __launch_bounds__(64) k_sa_lds_fast(const int32_t* __restrict__ 
         const uint2 x = *reinterpret_cast<const uint2*>(lv + 2 * (t * nw + (v >> 5)));
         return ((x.x ^ x.y) >> (v & 31)) & 1u;
     };
+    // This kernel keeps its own text of what the unit's helpers do (rows and
+    // majority, setup, state load, parser, accept test, write-back): with any
+    // subset of them shared, k_sa_lds_fast<4,1,false> needs more than 80 VGPRs
+    // (6 -> 5 waves) or its step is 1.5-2.7 % slower ("The LDS
+    // kernels' shared parts").  A fix to a helper must be repeated here.
     auto nbrs = [&](int v, int (&o)[D]) {
         const uint2 x = *reinterpret_cast<const uint2*>(rows + v * 4);
         o[0] = (int)(x.x & 0xffffu);
@@ -428,7 +678,7 @@ __global__ void __launch_bounds__(64) k_sa_lds_fast(const int32_t* __restrict__ 
         return (2 * ones > D) ? 1u : ((2 * ones < D) ? 0u : own);
     };
 
-    // ---- launch setup (as k_sa_lds)
+    // ---- launch setup
     for (int64_t q = lane; q < n * D; q += 64) {
         const int64_t v = q / D;
         rows[v * 4 + (q - v * D)] = (uint16_t)g[q];
@@ -721,11 +971,6 @@ __global__ void __launch_bounds__(64) k_sa_lds_fast(const int32_t* __restrict__ 
         const double t1 = (-2.0 * a) * si;
         const double t2 = b * (double)(sum_end - sum_new);
         const double num = t1 + t2;
-        // u < min(1, exp(-dE)) (code/SA_RRG.py:75-76) decided by an fp32 exp
-        // wherever u is farther from it than that exp's error (|x| * 2^-24 from
-        // rounding x, a few ulp from the exp itself: 1e-6 (1 + |x|) relative
-        // covers both); otherwise, and for the trace, the float64 dE and exp of
-        // the reference, unchanged.  Same decision bit for bit.
         const float xf = (float)(-num * inv_n);
         const float ef = __expf(xf);
         const float mg = ef * (1e-6f * (1.0f + fabsf(xf))) + 1e-37f;
@@ -776,12 +1021,7 @@ __global__ void __launch_bounds__(64) k_sa_lds_fast(const int32_t* __restrict__ 
         t += 1;                                                     // (code/SA_RRG.py:82)
         if (t > t_cap) done = 2;                                    // (code/SA_RRG.py:84)
         else if (sum_end == n) done = 1;                            // m(s_endstate(s)) == 1
-        if (TRACE && lane == 0) {
-            if (st.tr_i) st.tr_i[k * R + r] = iv;
-            if (st.tr_acc) st.tr_acc[k * R + r] = acc ? 1 : 0;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = dE;
-        }
+        if (TRACE && lane == 0) trace_step(st, k * R + r, iv, acc, sum_end, dE);
         wave_sync();
         LDS_STAMP(6);
     }
@@ -790,15 +1030,9 @@ __global__ void __launch_bounds__(64) k_sa_lds_fast(const int32_t* __restrict__ 
         for (int q = 0; q < 8; ++q) atomicAdd(&mjx_sa_lds_prof[q], _acc[q]);
 #endif
     // the stream index numpy would hold: the end of the last proposal consumed
+    // (the state in LDS is that proposal's: a window never runs past a twist)
     if (drew) idx = __builtin_amdgcn_readlane(pb_end, pk - 1);
-    if (TRACE && lane == 0) {
-        for (; k < nsteps; ++k) {
-            if (st.tr_i) st.tr_i[k * R + r] = -1;
-            if (st.tr_acc) st.tr_acc[k * R + r] = -1;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = 0.0;
-        }
-    }
+    if (TRACE && lane == 0) trace_tail(st, k, nsteps, R, r, sum_end);
     for (int64_t v0 = 0; v0 < n; v0 += 64) {
         const int v = (int)(v0 + lane);
         if (v < n && (((lword(0, v >> 5) ^ lev0s[v >> 5]) >> (v & 31)) & 1u))
@@ -1826,6 +2060,10 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_wg(const int32_t* __restrict
         return reinterpret_cast<uint32_t*>(mk + (t - 1) * mkl + (v & ~(MPW - 1)));
     };
     auto mark_bit = [&](int v) -> uint32_t { return obit << (MKB * (v & (MPW - 1))); };
+    // As k_sa_lds_fast, this kernel keeps its own text of what the unit's helpers
+    // do, its proposal ring included (k_sa_lds_cu's is `Ring`): through the
+    // helpers k_sa_lds_wg<3,2,8,false> went from 5 to 4 waves and the 4-wave step
+    // ran 0.9 % slower; only the whole of the own text gives the former code.
     auto nbrs = [&](int v, int (&o)[D]) {
         const uint2 x = *reinterpret_cast<const uint2*>(rows + v * 4);
         o[0] = (int)(x.x & 0xffffu);
@@ -1886,14 +2124,7 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_wg(const int32_t* __restrict
     double inv_n = 1.0 / (double)n;
     asm volatile("" : "+v"(a), "+v"(b), "+v"(par_a), "+v"(par_b), "+v"(a_cap), "+v"(b_cap), "+v"(inv_n));
 
-    // ---- the proposal ring (wave P = NE parses, the NE others evaluate): slot
-    // q & 63 holds proposal q of the launch (i, u, end: the MT index after its
-    // draws, bit 10 its state generation's parity).  npend proposals parsed, pk
-    // taken (running counts, every wave tracks pk); the parse wave appends while
-    // the round evaluates, into slots the round does not read, and keeps slot
-    // pk-1 (the last taken proposal's end) for the launch's MT position.  A twist
-    // under unconsumed proposals first saves the old state to st.mt: the launch
-    // ends on either generation (the buffer the last taken proposal drew from).
+    // ---- the proposal ring (wave P = NE parses, the NE others evaluate)
     uint32_t npend = 0, pk = 0;
     int gen = 0;
     const int idx0 = idx;
@@ -2182,8 +2413,6 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_wg(const int32_t* __restrict
         const double t1 = (-2.0 * ah) * si;
         const double t2 = bh * (double)(-ds);
         const double num = t1 + t2;
-        // u < min(1, exp(-dE)) by an fp32 exp where u is farther from it than that
-        // exp's error, else by the reference's float64 dE and exp (as k_sa_lds_fast)
         const float xf = (float)(-num * inv_n);
         const float ef = __expf(xf);
         const float mg = ef * (1e-6f * (1.0f + fabsf(xf))) + 1e-37f;
@@ -2283,13 +2512,7 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_wg(const int32_t* __restrict
         ties += __popcll(__ballot(lane < taken && ((pq >> 1) & 1u)));
         if constexpr (TRACE) {
             const int64_t my_sum = rl64(sum_after, w);              // sum(s_end) after this wave's step
-            if (w < taken && lane == 0) {
-                const int64_t kk = k + w;
-                if (st.tr_i) st.tr_i[kk * R + r] = iv;
-                if (st.tr_acc) st.tr_acc[kk * R + r] = ((accm >> w) & 1u) ? 1 : 0;
-                if (st.tr_sum) st.tr_sum[kk * R + r] = my_sum;
-                if (st.tr_dE) st.tr_dE[kk * R + r] = dE;
-            }
+            if (w < taken && lane == 0) trace_step(st, (k + w) * R + r, iv, (accm >> w) & 1u, my_sum, dE);
         }
         sum_end = rl64(sum_after, taken - 1);
         done = __builtin_amdgcn_readlane(dnq, taken - 1);
@@ -2333,14 +2556,7 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_wg(const int32_t* __restrict
         atomicAdd(&mjx_sa_lds_prof[16 + w], (unsigned long long)_acc[8]);
     }
 #endif
-    if (TRACE && tid == 0) {
-        for (; k < nsteps; ++k) {
-            if (st.tr_i) st.tr_i[k * R + r] = -1;
-            if (st.tr_acc) st.tr_acc[k * R + r] = -1;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = 0.0;
-        }
-    }
+    if (TRACE && tid == 0) trace_tail(st, k, nsteps, R, r, sum_end);
     __syncthreads();
     {
         const int64_t col = r >> 6;
@@ -2497,16 +2713,6 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
     auto lvl = [&](int t, int v) -> uint32_t { return ((uint32_t)mk[(t - 1) * mkl + v] >> LVB) & 1u; };
     auto mark_word = [&](int t, int v) -> uint32_t* { return reinterpret_cast<uint32_t*>(mk + (t - 1) * mkl + (v & ~1)); };
     auto row = [&](int v) -> uint2 { return *reinterpret_cast<const uint2*>(rows + v * 4); };
-    auto unpack = [&](uint2 x, int (&o)[D]) {
-        o[0] = (int)(x.x & 0xffffu);
-        o[1] = (int)(x.x >> 16);
-        o[2] = (int)(x.y & 0xffffu);
-        if constexpr (D > 3) o[3] = (int)(x.y >> 16);
-    };
-    auto nbrs = [&](int v, int (&o)[D]) { unpack(row(v), o); };
-    auto maj = [&](int ones, uint32_t own) -> uint32_t {       // always-stay majority (code/SA_RRG.py:19-20)
-        return (2 * ones > D) ? 1u : ((2 * ones < D) ? 0u : own);
-    };
     // the wave's items appended to a list (with their rows below the last
     // level): one LDS atomic per wave
     auto append = [&](uint32_t* list, uint2* lrow, uint32_t* counter, bool add, uint32_t entry, uint2 erow) {
@@ -2524,10 +2730,11 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
     // a ring entry's static neighbourhood, by the parse wave when it is parsed:
     // candidate j = 0..d of level 1 (i, then its neighbours), its row, whether
     // it repeats an earlier candidate, which of its neighbours are i
-    auto prep = [&](int slot, int iv) {
+    // (always_inline is load-bearing: as a call, its closure is 160 B of scratch per lane)
+    auto prep = [&](int slot, int iv) __attribute__((always_inline)) {
         const uint2 xi = row(iv);
         int ri[D];
-        unpack(xi, ri);
+        unpack_row<D>(xi, ri);
 #pragma unroll
         for (int j = 0; j <= D; ++j) {
             const int cand = (j == 0) ? iv : ri[j > 0 ? j - 1 : 0];
@@ -2538,7 +2745,7 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
             const bool dup = j > 0 && (cand == iv || first + 1 < j);
             const uint2 xc = (j == 0) ? xi : row(cand);
             int nv[D];
-            unpack(xc, nv);
+            unpack_row<D>(xc, nv);
             uint32_t eqm = 0;
 #pragma unroll
             for (int e = 0; e < D; ++e) eqm |= (nv[e] == iv ? 1u : 0u) << e;
@@ -2547,130 +2754,51 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
         }
     };
 
-    // ---- launch setup (k_sa_lds_wg's): rows, level 0, marks cleared, MT state; levels 1..T
+    // ---- launch setup: rows, level 0, marks cleared, MT state; levels 1..T
     {
         const int32_t* g = adj + (st.rep_graph ? (int64_t)st.rep_graph[r] : 0) * n * D;
-        for (int64_t q = tid; q < n * D; q += NT) {
-            const int64_t v = q / D;
-            rows[v * 4 + (q - v * D)] = (uint16_t)g[q];
-        }
+        stage_rows(rows, g, n, D, 4, tid, NT);
         for (int q = tid; q < nw; q += NT) lev[q] = 0u;
         for (int q = tid; q < T * nw * 16; q += NT) reinterpret_cast<uint32_t*>(mk)[q] = 0u;
-        for (int q = tid; q < MT_N; q += NT) mt[q] = st.mt[r * MT_N + q];
+        copy_mt(mt, st.mt + r * MT_N, tid, NT);
         if (tid < 32) {
             dsv[tid] = 0;
             cfv[tid] = 0u;
         }
         if (tid < 8) cnt[tid] = 0u;
-        const int64_t col = r >> 6;
-        const u64 rbit = 1ull << (r & 63);
         __syncthreads();
-        for (int64_t v0 = (int64_t)w * 64; v0 < (int64_t)nw * 32; v0 += NT) {
-            const int64_t v = v0 + lane;
-            const bool b = v < n && (s[v * W + col] & rbit);
-            const u64 m = __ballot(b);
-            if (lane < 2) {
-                const uint32_t x = (uint32_t)(m >> (32 * lane));
-                lev[(v0 >> 5) + lane] = x;
-                lev0s[(v0 >> 5) + lane] = x;
-            }
-        }
+        level0_from_s<1>(lev, lev0s, s, n, W, r, nw, lane, (int64_t)w * 64, NT);
         __syncthreads();
         for (int t = 1; t <= T; ++t) {
             for (int v = tid; v < n; v += NT) {
                 int nv[D];
-                nbrs(v, nv);
+                unpack_row<D>(rows, v, nv);
                 int ones = 0;
 #pragma unroll
                 for (int q = 0; q < D; ++q) ones += (int)(t == 1 ? bit_of(nv[q]) : lvl(t - 1, nv[q]));
-                const uint32_t nb = maj(ones, t == 1 ? bit_of(v) : lvl(t - 1, v));
+                const uint32_t nb = maj<D>(ones, t == 1 ? bit_of(v) : lvl(t - 1, v));
                 mk[(t - 1) * mkl + v] = (MK)(nb << LVB);
             }
             __syncthreads();
         }
     }
 
-    double a = st.a[r], b = st.b[r];
-    int64_t t = st.t[r], sum_end = st.sum_end[r];
-    int done = st.done[r];
-    int idx = st.mt_idx[r];
-    int ties = 0;
-    const uint32_t rng = (uint32_t)(n - 1);
-    uint32_t mask = rng;
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-    double inv_n = 1.0 / (double)n;
-    asm volatile("" : "+v"(a), "+v"(b), "+v"(par_a), "+v"(par_b), "+v"(a_cap), "+v"(b_cap), "+v"(inv_n));
+    double a, b, inv_n;
+    int64_t t, sum_end;
+    int done, idx, ties = 0;
+    uint32_t rng, mask;
+    load_state(st, r, n, a, b, t, sum_end, done, idx, rng, mask, inv_n, par_a, par_b, a_cap, b_cap);
 
-    // ---- the proposal ring, parsed by wave PW (k_sa_lds_wg's, and each entry's prep)
+    // ---- the proposal ring, parsed by wave PW, with each entry's prep
     uint32_t npend = 0, pk = 0;
     int gen = 0;
     const int idx0 = idx;
-    auto twist = [&]() {
-        for (int q = lane; q < MT_N; q += 64) st.mt[r * MT_N + q] = mt[q];
-        lds_twist(mt, lane);
-        idx = 0;
-        gen ^= 1;
+    const Ring ring{q_i, q_end, q_u, mt, st.mt + r * MT_N, rng, mask, lane, idx, gen, npend, pk};
+    // (always_inline here and on prep: without it prep is called and the kernel gets 160 B of scratch per lane)
+    auto parse_window = [&](uint32_t room) __attribute__((always_inline)) -> bool {
+        return ring_parse_window(ring, room, prep);
     };
-    auto twist_ok = [&]() -> bool {
-        const int lg = (pk > 0u) ? ((q_end[(pk - 1u) & 63u] >> 10) & 1) : 0;
-        return lg == gen || npend == pk;
-    };
-    auto parse_window = [&](uint32_t room) -> bool {
-        if (idx >= MT_N) {
-            if (!twist_ok()) return false;
-            twist();
-        }
-        const int lim = (MT_N - idx < 64) ? MT_N - idx : 64;
-        uint32_t tw = 0, y = 0;
-        bool ok = false;
-        if (lane < lim) {
-            tw = mt_temper(mt[idx + lane]);
-            y = tw & mask;
-            ok = y <= rng;
-        }
-        const u64 okm = __ballot(ok);
-        u64 stm = mt_window_starts(ok) & ((lim >= 2) ? ((1ull << (lim - 2)) - 1ull) : 0ull);
-        while ((uint32_t)__popcll(stm) > room) stm &= ~(1ull << (63 - __clzll(stm)));
-        const uint32_t got = (uint32_t)__popcll(stm);
-        const int pos = got ? 66 - __clzll(stm) : 0;
-        if (got > 0) {
-            const uint32_t x1 = mt_next_lane(tw);
-            const uint32_t x2 = mt_next_lane(x1);
-            if ((stm >> lane) & 1ull) {
-                const int q = (int)((npend + (uint32_t)__popcll(stm & ltmask)) & 63u);
-                q_i[q] = (int)y;
-                q_u[q] = mt_double(x1, x2);
-                q_end[q] = (idx + lane + 3) | (gen << 10);
-                prep(q, (int)y);
-            }
-            npend += got;
-            idx += pos;
-            return true;
-        }
-        if (room == 0) return true;
-        if (!okm) { idx += lim; return true; }
-        const int f = __ffsll((unsigned long long)okm) - 1;
-        if (f > 0) { idx += f; return true; }
-        if (idx + 2 >= MT_N && !twist_ok()) return false;
-        const int iv = __builtin_amdgcn_readlane((int)y, 0);
-        idx += 1;
-        if (idx >= MT_N) twist();
-        const uint32_t w1 = mt_temper(mt[idx]);
-        idx += 1;
-        if (idx >= MT_N) twist();
-        const uint32_t w2 = mt_temper(mt[idx]);
-        idx += 1;
-        if (lane == 0) {
-            const int q = (int)(npend & 63u);
-            q_i[q] = iv;
-            q_u[q] = mt_double(w1, w2);
-            q_end[q] = idx | (gen << 10);
-            prep(q, iv);
-        }
-        npend += 1;
-        return true;
-    };
-    auto room = [&]() -> uint32_t { return 63u - (npend - pk); };
+    auto room = [&]() __attribute__((always_inline)) -> uint32_t { return ring_room(ring); };
 
     int64_t k = 0;
     int par = 0;                                       // round parity: the list-length set in use
@@ -2742,12 +2870,12 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
                     xc = q_cr[slot * DP1 + j];
                     const int cand = (int)(ce & 0xffffu);
                     int nv[D];
-                    unpack(xc, nv);
+                    unpack_row<D>(xc, nv);
                     int ones = 0;
 #pragma unroll
                     for (int e = 0; e < D; ++e) ones += (int)(bit_of(nv[e]) ^ ((ce >> (17 + e)) & 1u));
                     const uint32_t own = bit_of(cand) ^ ((ce >> 21) & 1u);
-                    const uint32_t nb = maj(ones, own);
+                    const uint32_t nb = maj<D>(ones, own);
                     const uint32_t cur = lvl(1, cand);
                     add = !((ce >> 16) & 1u) && nb != cur;
                     if (add) atomicOr(mark_word(1, cand), (1u << q) << (16 * (cand & 1)));
@@ -2762,8 +2890,8 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
                     const int sq = (int)((pk + (uint32_t)q) & 63u), sj = (int)((pk + (uint32_t)j) & 63u);
                     const int iq = (int)(q_cn[sq * DP1] & 0xffffu), ij = (int)(q_cn[sj * DP1] & 0xffffu);
                     int rq[D], rj[D];
-                    unpack(q_cr[sq * DP1], rq);
-                    unpack(q_cr[sj * DP1], rj);
+                    unpack_row<D>(q_cr[sq * DP1], rq);
+                    unpack_row<D>(q_cr[sj * DP1], rj);
                     bool meet = iq == ij;
 #pragma unroll
                     for (int e = 0; e < D; ++e) meet |= (rj[e] == iq) | (ij == rq[e]);
@@ -2803,12 +2931,12 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
                         const uint2 xm = gln[l - 1][mi];
                         const int mc = (int)(me & 0xffffu), q = (int)((me >> 16) & 15u);
                         int nm2[D];
-                        unpack(xm, nm2);
+                        unpack_row<D>(xm, nm2);
                         const int c2 = (j == 0) ? mc : nm2[j > 0 ? j - 1 : 0];
                         const uint32_t early = (1u << q) - 1u;
                         xc = row(c2);
                         int nv2[D];
-                        unpack(xc, nv2);
+                        unpack_row<D>(xc, nv2);
                         int ones = 0;
                         uint32_t cfm = 0;
                         // node v at level l-1 as proposal q sees it; the earlier proposals' marks into cfm
@@ -2821,7 +2949,7 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
                         for (int e = 0; e < D; ++e) ones += (int)look(nv2[e]);
                         const uint32_t own = look(c2);
                         if (cfm) atomicOr(&cfp[q], cfm);
-                        const uint32_t nb = maj(ones, own);
+                        const uint32_t nb = maj<D>(ones, own);
                         const uint32_t cur = lvl(l, c2);
                         const bool chg = nb != cur;
                         const uint32_t mb = (1u << q) << (16 * (c2 & 1));
@@ -2863,24 +2991,9 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
         const uint32_t pcf = lq ? cfp[ql] : 0u;
         const double t2 = bh * (double)(-ds);
         const double num = t1 + t2;
-        bool acc;
-        bool tie = false;
-        double dE = 0.0;
-        {
-            const float xf = (float)(-num * inv_n);
-            const float ef = __expf(xf);
-            const float mg = ef * (1e-6f * (1.0f + fabsf(xf))) + 1e-37f;
-            if (fabs(u - (double)ef) > (double)mg) {
-                acc = u < (double)ef;
-                if (TRACE && st.tr_dE) dE = num / (double)n;
-            } else {
-                dE = num / (double)n;
-                const double e = exp(-dE);
-                const double prob = (e < 1.0) ? e : 1.0;
-                acc = u < prob;
-                tie = e < 1.0 && fabs(u - e) <= 4.0 * (nextafter(e, 2.0) - e);
-            }
-        }
+        bool tie;
+        double dE;
+        const bool acc = sa_accept_screened(num, inv_n, n, u, TRACE && st.tr_dE, dE, tie);
         LDS_STAMP(3);
         // ---- resolve in proposal order (every wave alike, k_sa_lds_wg's rule)
         const bool aq = lq && acc;
@@ -2906,14 +3019,8 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
         }
         ties += __popcll(__ballot(lane < taken && tie));
         if constexpr (TRACE) {
-            if (w == 0 && lane < taken) {
-                const int64_t kk = k + lane;
-                const int iv = q_i[(pk + (uint32_t)lane) & 63u];
-                if (st.tr_i) st.tr_i[kk * R + r] = iv;
-                if (st.tr_acc) st.tr_acc[kk * R + r] = acc ? 1 : 0;
-                if (st.tr_sum) st.tr_sum[kk * R + r] = sum_after;
-                if (st.tr_dE) st.tr_dE[kk * R + r] = dE;
-            }
+            if (w == 0 && lane < taken)
+                trace_step(st, (k + lane) * R + r, q_i[(pk + (uint32_t)lane) & 63u], acc, sum_after, dE);
         }
         sum_end = rl64(sum_after, taken - 1);
         done = __builtin_amdgcn_readlane(dnq, taken - 1);
@@ -2964,36 +3071,16 @@ __global__ void __launch_bounds__(64 * NW) k_sa_lds_cu(const int32_t* __restrict
         atomicAdd(&mjx_sa_lds_prof[15], (unsigned long long)_acc[5]);
     }
 #endif
-    if (TRACE && tid == 0) {
-        for (; k < nsteps; ++k) {
-            if (st.tr_i) st.tr_i[k * R + r] = -1;
-            if (st.tr_acc) st.tr_acc[k * R + r] = -1;
-            if (st.tr_sum) st.tr_sum[k * R + r] = sum_end;
-            if (st.tr_dE) st.tr_dE[k * R + r] = 0.0;
-        }
-    }
+    if (TRACE && tid == 0) trace_tail(st, k, nsteps, R, r, sum_end);
     __syncthreads();
-    {
-        const int64_t col = r >> 6;
-        for (int64_t v = tid; v < n; v += NT) {
-            if (((lev[v >> 5] ^ lev0s[v >> 5]) >> (v & 31)) & 1u)
-                atomicXor((unsigned long long*)&s[v * W + col], 1ull << (r & 63));
-        }
-    }
+    write_back_level0<1>(lev, lev0s, s, n, W, r, tid, NT);
     if (w == PW) {
+        // the launch's MT position, as k_sa_lds_wg hands it back
         const int e = (pk > 0) ? q_end[(pk - 1u) & 63u] : idx0;
-        if (((e >> 10) & 1) == gen)
-            for (int q = lane; q < MT_N; q += 64) st.mt[r * MT_N + q] = mt[q];
+        if (((e >> 10) & 1) == gen) copy_mt(st.mt + r * MT_N, mt, lane, 64);
         if (lane == 0) st.mt_idx[r] = e & 1023;
     }
-    if (tid == 0) {
-        st.a[r] = a;
-        st.b[r] = b;
-        st.t[r] = t;
-        st.sum_end[r] = sum_end;
-        st.done[r] = done;
-        if (st.tr_tie) st.tr_tie[r] += ties;
-    }
+    if (tid == 0) store_state(st.a, st.b, st.t, st.sum_end, st.done, st.tr_tie, r, a, b, t, sum_end, done, ties);
 }
 
 // ---------------------------------------------------------------------------
@@ -3453,41 +3540,70 @@ extern "C" int64_t mjx_sa_lds_bytes(int64_t n, int d, int p, int c) {
     return g.bytes;
 }
 
-// The LDS bytes and threads per workgroup of the kernel mjx_sa_lds_steps runs
-// for (n, d, p, c) and the kernel options (opt_flags, opt_split): the same
-// selection as mjx_sa_lds_steps below.
-extern "C" int64_t mjx_sa_lds_plan(int64_t n, int d, int p, int c, uint32_t flags, int split, int* threads) {
-    if (p < 0 || c < 0) return -1;
-    const int T = p + c - 1;
-    salds::Geo g;
-    if (!salds::geometry(n, d, T, &g)) return -1;
-    int th = 64;
-    int64_t bytes = g.bytes;
-    const bool small_d = d == 3 || d == 4;
+// The kernel that runs for (n, d, T = p+c-1) and the kernel options (opt_flags,
+// opt_split), with its geometry, threads per workgroup and dynamic LDS bytes:
+// what mjx_sa_lds_plan reports and mjx_sa_lds_steps launches.
+namespace {
+enum class Kind { Serial, Fast, Pair, Multi, Wg1, Wg, Cu };
+struct Plan {
+    Kind kind;
+    int waves;          // of the whole-CU kernels (k_sa_lds_wg1: 4 and the parser)
+    int threads, bytes;
+    salds::Geo g;       // the one-wave kernels' (k_sa_lds_pair: two mark planes)
     salds::GeoW gw;
-    salds::Geo g2;
-    const int nwv = salds::wg_waves(n, d, T, split);
-    salds::GeoW1 gw1;
     salds::GeoC gc;
-    if (salds::use_cu(n, d, T, flags, split, &gc)) {
-        th = 64 * salds::cu_waves(split);           // k_sa_lds_cu: item waves + the parser
-        bytes = gc.bytes;
-    } else if (!(flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR | MJX_SA_LDS_WAVE)) && small_d && T == 1 &&
-        salds::geometry_wg1(n, d, 32, &gw1)) {
-        th = 320;                                   // k_sa_lds_wg1: 4 waves x 8 proposals + the parser
-        bytes = gw1.bytes;
-    } else if (!(flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR)) && small_d && T == 1) {
-        // k_sa_lds_multi: the one-plane geometry
-    } else if (!(flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_WAVE)) && small_d && T >= 2 && T <= 4 &&
-               salds::geometry_wg(n, d, T, nwv, &gw)) {
-        th = 64 * nwv;
-        bytes = gw.bytes;
-    } else if (!(flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE)) && small_d && T <= 4 &&
-               salds::geometry(n, d, T, &g2, 2)) {
-        bytes = g2.bytes;
+    salds::GeoW1 gw1;
+};
+
+bool select(int64_t n, int d, int T, uint32_t flags, int split, Plan* pl) {
+    if (!salds::geometry(n, d, T, &pl->g)) return false;
+    pl->kind = Kind::Serial;
+    pl->waves = 1;
+    pl->bytes = pl->g.bytes;
+    const bool small_d = d == 3 || d == 4;
+    const auto none = [&](uint32_t opts) { return !(flags & opts); };
+    salds::Geo g2;
+    if (salds::use_cu(n, d, T, flags, split, &pl->gc)) {
+        pl->kind = Kind::Cu;                        // item waves + the parser
+        pl->waves = salds::cu_waves(split);
+        pl->bytes = pl->gc.bytes;
+    } else if (none(MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR | MJX_SA_LDS_WAVE) && small_d && T == 1 &&
+               salds::geometry_wg1(n, d, 32, &pl->gw1)) {
+        pl->kind = Kind::Wg1;                       // 4 waves x 8 proposals + the parser
+        pl->waves = 5;
+        pl->bytes = pl->gw1.bytes;
+    } else if (none(MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR) && small_d && T == 1) {
+        pl->kind = Kind::Multi;                     // the one-plane geometry
+    } else if (none(MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_WAVE) && small_d && T >= 2 && T <= 4 &&
+               salds::geometry_wg(n, d, T, salds::wg_waves(n, d, T, split), &pl->gw)) {
+        pl->kind = Kind::Wg;
+        pl->waves = salds::wg_waves(n, d, T, split);
+        pl->bytes = pl->gw.bytes;
+    } else if (none(MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE) && small_d && T <= 4 && salds::geometry(n, d, T, &g2, 2)) {
+        pl->kind = Kind::Pair;
+        pl->g = g2;
+        pl->bytes = g2.bytes;
+    } else if (none(MJX_SA_LDS_SERIAL) && small_d && T <= 4) {
+        pl->kind = Kind::Fast;
     }
-    if (threads) *threads = th;
-    return bytes;
+    pl->threads = 64 * pl->waves;
+    return true;
+}
+
+template <class K, class... A>
+int launch(K kern, const char* name, int64_t R, const Plan& pl, hipStream_t hs, A... args) {
+    MJX_HIP(set_max_lds(kern, pl.bytes), "sa_lds lds");
+    kern<<<(unsigned)R, pl.threads, (size_t)pl.bytes, hs>>>(args...);
+    MJX_LAUNCH_CHECK(name);
+    return MJX_OK;
+}
+}  // namespace
+
+extern "C" int64_t mjx_sa_lds_plan(int64_t n, int d, int p, int c, uint32_t flags, int split, int* threads) {
+    Plan pl;
+    if (p < 0 || c < 0 || !select(n, d, p + c - 1, flags, split, &pl)) return -1;
+    if (threads) *threads = pl.threads;
+    return pl.bytes;
 }
 
 extern "C" int mjx_sa_lds_steps(const int32_t* adj, int64_t n, int d, int p, int c, int64_t R, uint64_t* s,
@@ -3496,145 +3612,72 @@ extern "C" int mjx_sa_lds_steps(const int32_t* adj, int64_t n, int d, int p, int
     if (!stp || !adj || !s || R < 1 || nsteps < 0 || p < 0 || c < 0) return MJX_EINVAL;
     if (stp->philox_key) return MJX_EINVAL;             // the LDS kernels replay MT19937 inside the step
     const int T = p + c - 1;
-    salds::Geo g;
-    if (!salds::geometry(n, d, T, &g)) return MJX_ERANGE;
     const mjx_sa_state st = *stp;
+    salds::Geo g0;      // only for the order of the return codes: ERANGE before any EINVAL, select() after the flag check
+    if (!salds::geometry(n, d, T, &g0)) return MJX_ERANGE;
     if (!st.mt || !st.mt_idx || !st.a || !st.b || !st.t || !st.sum_end || !st.done) return MJX_EINVAL;
     if (st.opt_flags & ~(MJX_SA_NO_SPEC | MJX_SA_NO_CONE2 | MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR |
                          MJX_SA_LDS_WAVE | MJX_SA_LDS_CU))
         return MJX_EINVAL;
+    Plan pl;
+    if (!select(n, d, T, st.opt_flags, st.opt_split, &pl)) return MJX_ERANGE;
     if (nsteps == 0) return MJX_OK;
     if (R > INT32_MAX) return MJX_ERANGE;
     const int64_t W = (R + 63) / 64;
     hipStream_t hs = as_stream(stream);
-    salds::GeoC gc;
-    if (salds::use_cu(n, d, T, st.opt_flags, st.opt_split, &gc)) {
-        const bool trc = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-        const int nwc = salds::cu_waves(st.opt_split);
-        auto goc = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, gc.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 64 * nwc, (size_t)gc.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b,
-                                                                  a_cap, b_cap, t_cap, gc);   // item waves + the parser
-            MJX_LAUNCH_CHECK("k_sa_lds_cu");
-            return MJX_OK;
-        };
-#define MJX_LDS_CU(DD, NN)                                                                                          \
-        if (T == 2) return trc ? goc(salds::k_sa_lds_cu<DD, 2, NN, true>) : goc(salds::k_sa_lds_cu<DD, 2, NN, false>); \
-        return trc ? goc(salds::k_sa_lds_cu<DD, 3, NN, true>) : goc(salds::k_sa_lds_cu<DD, 3, NN, false>);
-        if (nwc == 16) {
-            if (d == 3) { MJX_LDS_CU(3, 16) }
-            MJX_LDS_CU(4, 16)
-        }
-        if (d == 3) { MJX_LDS_CU(3, 8) }
-        MJX_LDS_CU(4, 8)
-#undef MJX_LDS_CU
-    }
-    auto go = [&](auto kern) -> int {
-        MJX_HIP(set_max_lds(kern, g.bytes), "sa_lds lds");
-        kern<<<(unsigned)R, 64, (size_t)g.bytes, hs>>>(adj, d, n, T, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap,
-                                                       b_cap, t_cap, g);
-        MJX_LAUNCH_CHECK("k_sa_lds");
-        return MJX_OK;
+    const bool trace = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
+    auto go = [&](auto kern, const char* name, const auto& geo) -> int {
+        return launch(kern, name, R, pl, hs, adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap, b_cap, t_cap, geo);
     };
-    salds::GeoW1 gw1;
-    if (!(st.opt_flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR | MJX_SA_LDS_WAVE)) &&
-        (d == 3 || d == 4) && T == 1 && salds::geometry_wg1(n, d, 32, &gw1)) {
-        const bool trw = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-        auto gow1 = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, gw1.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 320, (size_t)gw1.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap,
-                                                              b_cap, t_cap, gw1);          // 4 waves + the parser
-            MJX_LAUNCH_CHECK("k_sa_lds_wg1");
-            return MJX_OK;
-        };
-        if (d == 3) return trw ? gow1(salds::k_sa_lds_wg1<3, 4, 8, true>) : gow1(salds::k_sa_lds_wg1<3, 4, 8, false>);
-        return trw ? gow1(salds::k_sa_lds_wg1<4, 4, 8, true>) : gow1(salds::k_sa_lds_wg1<4, 4, 8, false>);
+    // KERN<d, ..., TRACE> for d = 3, 4: with trace buffers or without
+#define MJX_LDS_GO(GEO, KERN, ...)                                                                       \
+    return trace ? go(salds::KERN<__VA_ARGS__, true>, #KERN, GEO) : go(salds::KERN<__VA_ARGS__, false>, #KERN, GEO)
+#define MJX_LDS_D(GEO, KERN, ...)                         \
+    if (d == 3) { MJX_LDS_GO(GEO, KERN, 3, __VA_ARGS__); } \
+    MJX_LDS_GO(GEO, KERN, 4, __VA_ARGS__)
+#define MJX_LDS_T(GEO, KERN)                        \
+    switch (T) {                                    \
+        case 1: { MJX_LDS_D(GEO, KERN, 1); }        \
+        case 2: { MJX_LDS_D(GEO, KERN, 2); }        \
+        case 3: { MJX_LDS_D(GEO, KERN, 3); }        \
+        default: { MJX_LDS_D(GEO, KERN, 4); }       \
     }
-    if (!(st.opt_flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_PAIR)) && (d == 3 || d == 4) && T == 1) {
-        const bool trm = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-        auto gom = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, g.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 64, (size_t)g.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap,
-                                                           b_cap, t_cap, g);
-            MJX_LAUNCH_CHECK("k_sa_lds_multi");
-            return MJX_OK;
-        };
-        if (d == 3) return trm ? gom(salds::k_sa_lds_multi<3, 8, true>) : gom(salds::k_sa_lds_multi<3, 8, false>);
-        return trm ? gom(salds::k_sa_lds_multi<4, 8, true>) : gom(salds::k_sa_lds_multi<4, 8, false>);
+#define MJX_LDS_WG(NN)                                        \
+    switch (T) {                                              \
+        case 2: { MJX_LDS_D(pl.gw, k_sa_lds_wg, 2, NN); }     \
+        case 3: { MJX_LDS_D(pl.gw, k_sa_lds_wg, 3, NN); }     \
+        default: { MJX_LDS_D(pl.gw, k_sa_lds_wg, 4, NN); }    \
     }
-    salds::GeoW gw;
-    const int nwv = salds::wg_waves(n, d, T, st.opt_split);
-    if (!(st.opt_flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE | MJX_SA_LDS_WAVE)) && (d == 3 || d == 4) && T >= 2 &&
-        T <= 4 && salds::geometry_wg(n, d, T, nwv, &gw)) {
-        const bool trw = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-        auto gow = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, gw.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 64 * nwv, (size_t)gw.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b,
-                                                                 a_cap, b_cap, t_cap, gw);
-            MJX_LAUNCH_CHECK("k_sa_lds_wg");
-            return MJX_OK;
-        };
-#define MJX_LDS_WG3(DD, TT)                                                                                       \
-        if (nwv == 4) return trw ? gow(salds::k_sa_lds_wg<DD, TT, 4, true>) : gow(salds::k_sa_lds_wg<DD, TT, 4, false>); \
-        if (nwv == 16) return trw ? gow(salds::k_sa_lds_wg<DD, TT, 16, true>) : gow(salds::k_sa_lds_wg<DD, TT, 16, false>); \
-        return trw ? gow(salds::k_sa_lds_wg<DD, TT, 8, true>) : gow(salds::k_sa_lds_wg<DD, TT, 8, false>);
-#define MJX_LDS_WG(DD)                       \
-        switch (T) {                         \
-            case 2: { MJX_LDS_WG3(DD, 2) }   \
-            case 3: { MJX_LDS_WG3(DD, 3) }   \
-            default: { MJX_LDS_WG3(DD, 4) }  \
-        }
-        if (d == 3) { MJX_LDS_WG(3) }
-        MJX_LDS_WG(4)
+#define MJX_LDS_CU(NN)                                        \
+    if (T == 2) { MJX_LDS_D(pl.gc, k_sa_lds_cu, 2, NN); }     \
+    MJX_LDS_D(pl.gc, k_sa_lds_cu, 3, NN)
+    switch (pl.kind) {
+        case Kind::Cu:
+            if (pl.waves == 16) { MJX_LDS_CU(16); }
+            MJX_LDS_CU(8);
+        case Kind::Wg1: MJX_LDS_D(pl.gw1, k_sa_lds_wg1, 4, 8);
+        case Kind::Multi: MJX_LDS_D(pl.g, k_sa_lds_multi, 8);
+        case Kind::Wg:
+            if (pl.waves == 4) { MJX_LDS_WG(4) }
+            if (pl.waves == 16) { MJX_LDS_WG(16) }
+            MJX_LDS_WG(8)
+        case Kind::Pair: MJX_LDS_T(pl.g, k_sa_lds_pair)
+        case Kind::Fast: MJX_LDS_T(pl.g, k_sa_lds_fast)
+        case Kind::Serial: break;
+    }
+#undef MJX_LDS_CU
 #undef MJX_LDS_WG
-#undef MJX_LDS_WG3
-    }
-    salds::Geo g2;
-    if (!(st.opt_flags & (MJX_SA_LDS_SERIAL | MJX_SA_LDS_SINGLE)) && (d == 3 || d == 4) && T <= 4 &&
-        salds::geometry(n, d, T, &g2, 2)) {
-        auto gop = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, g2.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 64, (size_t)g2.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap,
-                                                            b_cap, t_cap, g2);
-            MJX_LAUNCH_CHECK("k_sa_lds_pair");
-            return MJX_OK;
-        };
-        const bool trp = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-#define MJX_LDS_PAIR(DD)                                                                                   \
-        switch (T) {                                                                                       \
-            case 1: return trp ? gop(salds::k_sa_lds_pair<DD, 1, true>) : gop(salds::k_sa_lds_pair<DD, 1, false>); \
-            case 2: return trp ? gop(salds::k_sa_lds_pair<DD, 2, true>) : gop(salds::k_sa_lds_pair<DD, 2, false>); \
-            case 3: return trp ? gop(salds::k_sa_lds_pair<DD, 3, true>) : gop(salds::k_sa_lds_pair<DD, 3, false>); \
-            default: return trp ? gop(salds::k_sa_lds_pair<DD, 4, true>) : gop(salds::k_sa_lds_pair<DD, 4, false>); \
-        }
-        if (d == 3) { MJX_LDS_PAIR(3) }
-        MJX_LDS_PAIR(4)
-#undef MJX_LDS_PAIR
-    }
-    if (!(st.opt_flags & MJX_SA_LDS_SERIAL) && (d == 3 || d == 4) && T <= 4) {
-        auto gof = [&](auto kern) -> int {
-            MJX_HIP(set_max_lds(kern, g.bytes), "sa_lds lds");
-            kern<<<(unsigned)R, 64, (size_t)g.bytes, hs>>>(adj, n, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap,
-                                                           b_cap, t_cap, g);
-            MJX_LAUNCH_CHECK("k_sa_lds_fast");
-            return MJX_OK;
-        };
-        const bool tr = st.tr_i || st.tr_acc || st.tr_sum || st.tr_dE;
-#define MJX_LDS_FAST(DD)                                                                                   \
-        switch (T) {                                                                                       \
-            case 1: return tr ? gof(salds::k_sa_lds_fast<DD, 1, true>) : gof(salds::k_sa_lds_fast<DD, 1, false>); \
-            case 2: return tr ? gof(salds::k_sa_lds_fast<DD, 2, true>) : gof(salds::k_sa_lds_fast<DD, 2, false>); \
-            case 3: return tr ? gof(salds::k_sa_lds_fast<DD, 3, true>) : gof(salds::k_sa_lds_fast<DD, 3, false>); \
-            default: return tr ? gof(salds::k_sa_lds_fast<DD, 4, true>) : gof(salds::k_sa_lds_fast<DD, 4, false>); \
-        }
-        if (d == 3) { MJX_LDS_FAST(3) }
-        MJX_LDS_FAST(4)
-#undef MJX_LDS_FAST
-    }
+#undef MJX_LDS_T
+#undef MJX_LDS_D
+#undef MJX_LDS_GO
+    auto serial = [&](auto kern) -> int {
+        return launch(kern, "k_sa_lds", R, pl, hs, adj, d, n, T, R, W, (u64*)s, st, nsteps, par_a, par_b, a_cap, b_cap,
+                      t_cap, pl.g);
+    };
     switch (d) {
-        case 3: return go(salds::k_sa_lds<3>);
-        case 4: return go(salds::k_sa_lds<4>);
-        case 6: return go(salds::k_sa_lds<6>);
-        default: return go(salds::k_sa_lds<0>);
+        case 3: return serial(salds::k_sa_lds<3>);
+        case 4: return serial(salds::k_sa_lds<4>);
+        case 6: return serial(salds::k_sa_lds<6>);
+        default: return serial(salds::k_sa_lds<0>);
     }
 }

@@ -155,6 +155,12 @@ def test_sa_run_distinct_graphs_to_consensus(mjx_mod, n, N_stat, seed, graph_see
     (4, 1000, 3, 1, {"split": 4}), (4, 1000, 3, 1, {"lds_wave": True}), (4, 1000, 1, 1, {"lds_wave": True}),
     (4, 1000, 3, 1, {"lds_cu": True}), (4, 64, 3, 1, {"lds_cu": True}), (3, 500, 2, 1, {"lds_cu": True}),
     (4, 1000, 3, 1, {"lds_cu": True, "split": 16}),
+    # n = 64: the most proposals and rejected words per window, twists inside both calls
+    (4, 64, 3, 1, {"lds_single": True}), (4, 64, 1, 1, {"lds_single": True}),        # k_sa_lds_fast<4,T,false>
+    (4, 64, 1, 1, {"lds_pair": True}),                                                # k_sa_lds_pair<4,1,false>
+    (4, 64, 3, 1, {"lds_serial": True}),                                              # k_sa_lds<4>
+    (5, 64, 2, 1, {}), (6, 64, 2, 1, {}),                                             # k_sa_lds<0>, k_sa_lds<6>
+    (3, 64, 2, 3, {}),                                                                # k_sa_lds_wg<3,4,NW,false>
 ])
 def test_lds_no_trace_matches_oracle(mjx_mod, d, n, p, c, kernel):
     """The kernels run() and the bench use (no trace buffers: TRACE=false

@@ -2,7 +2,7 @@
 replicas on distinct graphs): p=c=1 (configs[0]) and p=3, c=1 (the script),
 LDS-resident replicas (every LDS kernel) vs the HBM cone layout.
 
-    python tools/sa_probe3.py [--no-cone] [--R 64] [--n 10000]
+    python tools/sa_probe3.py [--no-cone] [--R 64] [--n 10000] [--K 20000]
 """
 import argparse
 import os
@@ -18,7 +18,12 @@ ap.add_argument("--no-cone", action="store_true")
 ap.add_argument("--R", type=int, default=64)
 ap.add_argument("--n", type=int, default=10_000)
 ap.add_argument("--pc", default="1,1;3,1")
+ap.add_argument("--K", type=int, default=None,
+                help="steps of the warm-up and of the timed call (default 20000; the cone layout at p > 1: 1000); "
+                     "a line is a step time only while it prints done 0/R")
 args = ap.parse_args()
+if args.K is not None and args.K < 1:
+    ap.error("--K must be at least 1")
 n, d, R = args.n, 4, args.R
 graphs = [mjx.random_regular_graph(d, n, seed=7000 + k) for k in range(R)]
 VARIANTS = {
@@ -44,7 +49,7 @@ for pc in args.pc.split(";"):
             continue
         if name in ("lds-wg4", "lds-wg8", "lds-wg16", "lds-cu", "lds-cu16") and p + c - 1 < 2:
             continue
-        K = 20000 if (layout == "lds" or p == 1) else 1000
+        K = args.K if args.K is not None else (20000 if (layout == "lds" or p == 1) else 1000)
         sa = mjx.SAReplicas(graphs, p, c, list(range(R)), layout=layout, kernel=kern)
         sa.steps(K)
         torch.cuda.synchronize()
@@ -52,5 +57,5 @@ for pc in args.pc.split(";"):
         sa.steps(K)
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
-        print(f"p={p} c={c} {name}: {1e6 * el / K:.3f} us/step, {R * K / el:.3g} proposals/s, "
+        print(f"p={p} c={c} {name}: {1e6 * el / K:.4f} us/step, {R * K / el:.3g} proposals/s, "
               f"done {int((sa.done != 0).sum())}/{R}", flush=True)
