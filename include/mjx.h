@@ -877,6 +877,56 @@ int mjx_quench_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, i
                         uint64_t* out_np, int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag,
                         void* stream);
 
+/* ---- exact consensus census of a small graph ------------------------------- */
+/*
+ * Ground truth by exhaustive enumeration: every start configuration of a graph
+ * of n <= 48 nodes is run T = p + c - 1 steps (0 <= T <= 6, the rule of the
+ * quench calls) and counted when it has reached all +1.  G is an ELL (n, d) or
+ * CSR graph with symmetric adjacency, the always-stay majority rule of the
+ * sweeps (sign(2S+s), row entries count with multiplicity), a node of degree 0
+ * keeps its spin; a row holds at most 47 entries.
+ *   Configuration index: x in [0, 2^n); node v is +1 iff bit v of x is set; the
+ *     weight is k(x) = popcount(x).
+ *   64-config block: block b holds x = 64 b .. 64 b + 63; there are
+ *     B = 2^max(n-6, 0) blocks.  For n < 6 only the first 2^n bit positions of
+ *     block 0 are configurations; the rest is masked out.
+ *   Counts: for t = 0..T, counts[t][k] = #{x : k(x) = k and onestep^t(x) is all
+ *     +1}.  All +1 is a fixed point of the rule, so counts[t] <= counts[t+1]
+ *     elementwise; counts[0] is 1 at k = n and 0 elsewhere.  One enumeration
+ *     gives the whole dependence on p.
+ *   Witness: for each t the configuration with the smallest (k(x), x) in
+ *     lexicographic order among those counted in counts[t], as the key
+ *     k(x) << 48 | x.  It does not depend on the launch geometry or on how the
+ *     range of blocks is split.
+ *
+ * A lane owns one block at a time and walks a grid-stride loop over
+ * [block_lo, block_hi); the configurations are generated in place (node v < 6
+ * is a constant bit pattern, node v >= 6 is all ones iff bit v-6 of b is set),
+ * so nothing is read from memory but the adjacency.  The workgroup is one wave;
+ * its LDS holds two levels as [node][lane] words, its counts and keys, the
+ * level-0 patterns and the adjacency: mjx_census_lds(n) =
+ *   1024 n + 56 (n + 2) + 8 n + 8 ceil((n + 1) / 4) + 8 ceil(47 n / 8)
+ * bytes (-1 for n outside 1..48; 54,696 at n = 48, no dynamic-LDS opt-in).
+ *
+ * counts: device [T+1][n+1], ADDED to (64-bit atomics); witness_key: device
+ * [T+1], atomic-min'ed into (the caller starts it at all ones; a level nobody
+ * reaches keeps that value); so a caller may split [0, B) over several launches
+ * into the same buffers.  flag: one device int32 the caller zeroes, OR'ed into:
+ * bit 1 = an adjacency entry outside 0..n-1, bit 2 = a CSR row longer than 47
+ * entries or a row_ptr that does not start at 0 or decreases; the kernel then
+ * stops in bounds and the results are void.  grid: 0 = the library's choice,
+ * > 0 forces the number of workgroups.  block_lo = block_hi does nothing.
+ * MJX_ERANGE: n > 48, T > 6, d > 47.  MJX_EINVAL: n < 1, p or c < 0, T < 0, a
+ * block range outside 0 <= block_lo <= block_hi <= B, grid < 0, a NULL pointer.
+ * No allocation, no host synchronisation.
+ */
+int64_t mjx_census_lds(int64_t n);
+int mjx_census_ell(const int32_t* adj, int64_t n, int d, int p, int c, int64_t block_lo, int64_t block_hi, int grid,
+                   unsigned long long* counts, unsigned long long* witness_key, int32_t* flag, void* stream);
+int mjx_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t block_lo,
+                   int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
+                   int32_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm|attractor|quench`` run the reference's three
+"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm|attractor|quench|census`` run the reference's three
 experiments with its module constants as flags -- same names, same defaults --
 and write its np.savez keys.
 
@@ -29,6 +29,11 @@ and write its np.savez keys.
         order) jobs in one call (quench.quench_restarts), a graph per replica
         for ``graphs`` files; the same keys for the best restart plus
         mag_restarts (R, K) and best
+  census  no reference script: the exact consensus census (census.census) of
+        one small random regular or Erdos-Renyi graph (n <= 48, isolated nodes
+        kept), every one of the 2^n starts run p + c - 1 steps; output
+        "census_{graph}.npz": counts, min_plus, m_min, witness, entropy,
+        configs, edges
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -172,6 +177,17 @@ def build_parser():
                          "walking np.random.default_rng([S, r, k]).permutation(n) with S = --order-seed (required); "
                          "0: one pass as above")
     qu.add_argument("--out", default=None, help="output .npz (default: the input's name + _quenched)")
+    ce = sub.add_parser("census", help="count the starts of a small graph that reach consensus, all 2^n of them "
+                                       "(no reference script)")
+    ce.add_argument("--graph", choices=("rrg", "er"), default="rrg")
+    ce.add_argument("--n", type=int, default=24, help="nodes (at most 48; 2^n configurations are run)")
+    ce.add_argument("--d", type=int, default=3, help="degree (rrg)")
+    ce.add_argument("--deg", type=float, default=2.0, help="mean degree (er; prob = deg/(n-1))")
+    ce.add_argument("--graph-seed", type=int, default=0, help="seed of the graph")
+    ce.add_argument("--p", type=int, required=True)
+    ce.add_argument("--c", type=int, required=True)
+    ce.add_argument("--max-configs", type=int, default=2 ** 36, help="refuse a larger 2^n")
+    ce.add_argument("--out", default=None, help="output .npz (default: census_{graph}.npz)")
     return ap
 
 
@@ -367,10 +383,35 @@ def run_quench(a):
     return res
 
 
+def run_census(a):
+    from .census import census
+    from .graph import Graph, erdos_renyi, random_regular_graph
+    t0 = time.time()
+    if a.graph == "rrg":
+        adj = random_regular_graph(a.d, a.n, seed=a.graph_seed)
+        g = adj
+        u = np.repeat(np.arange(a.n), a.d)
+        v = np.asarray(adj).reshape(-1)
+    else:
+        rp, col = erdos_renyi(a.n, a.deg / (a.n - 1), seed=a.graph_seed)[:2]
+        g = Graph.csr(rp, col)
+        u = np.repeat(np.arange(a.n), np.diff(rp))
+        v = np.asarray(col)
+    res = census(g, a.p, a.c, max_configs=a.max_configs)
+    keep = u < v
+    res["edges"] = np.stack([u[keep], v[keep]], axis=1).astype(np.int64)
+    out = a.out or f"census_{a.graph}.npz"
+    np.savez(out, **res)
+    print(f"census: {a.graph} n={a.n}, 2^{a.n} configurations, p={a.p} c={a.c}: min_plus "
+          f"{res['min_plus'].tolist()}, m_min {np.round(res['m_min'], 4).tolist()}, reached "
+          f"{res['counts'].sum(axis=1).tolist()}, {time.time() - t0:.1f} s -> {out}", flush=True)
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm, "attractor": run_attractor,
-            "quench": run_quench}[a.cmd](a)
+            "quench": run_quench, "census": run_census}[a.cmd](a)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,293 @@
+// Exact consensus census of a small graph (no reference counterpart;
+// definitions in include/mjx.h): every configuration x in [0, 2^n) is run T
+// steps of the always-stay majority rule and counts[t][popcount(x)] counts the
+// x whose onestep^t(x) is all +1; the smallest (popcount(x), x) of every level
+// is its witness.
+//
+// A lane owns one 64-config block b at a time: bit j of every word it touches
+// is configuration x = 64 b + j.  Level 0 is never stored: node v < 6 is the
+// constant pattern "bit v of j" (a table of n words in LDS, 0 for v >= 6), node
+// v >= 6 is all ones iff bit v-6 of b is set -- one OR of the two, no branch on
+// v.  Levels 1..T ping-pong between two LDS buffers laid out [node][lane]
+// u64: the lanes of a wave read node u at base(u) + 8 lane (conflict-free
+// ds_read_b64, the neighbour index is wave-uniform), and a lane only ever
+// reads the words it wrote itself, so the sweeps need no barrier.  The
+// adjacency sits in LDS as bytes (n <= 48) behind u16 row offsets.
+//
+// The workgroup is one wave.  Everything is integer; no flags needed.
+#include "mjx_common.h"
+#include <algorithm>
+
+namespace mjx {
+
+constexpr int CN_MAXN = 48;
+constexpr int CN_MAXT = 6;
+constexpr int CN_MAXDEG = 47;                 // BitCounter<6>; a simple graph on 48 nodes has no longer row
+constexpr size_t kCnLdsMax = 64 * 1024;       // no dynamic-LDS opt-in needed
+constexpr size_t kCnLdsPerCu = 160 * 1024;    // gfx950: what the workgroups resident on a CU share
+
+constexpr int CN_FLAG_RANGE = 2;              // an adjacency entry outside 0..n-1 (bit 1, as mjx_quench_jobs_*)
+constexpr int CN_FLAG_ROW = 4;                // a row longer than CN_MAXDEG, or a decreasing row_ptr
+
+// C_w: the bit positions j of a word with popcount(j) = w
+constexpr u64 cn_weight_mask(int w) {
+    u64 m = 0;
+    for (int j = 0; j < 64; ++j) {
+        int pc = 0;
+        for (int k = 0; k < 6; ++k) pc += (j >> k) & 1;
+        if (pc == w) m |= 1ull << j;
+    }
+    return m;
+}
+
+constexpr u64 kCnWeight[7] = {cn_weight_mask(0), cn_weight_mask(1), cn_weight_mask(2), cn_weight_mask(3),
+                              cn_weight_mask(4), cn_weight_mask(5), cn_weight_mask(6)};
+
+__device__ __forceinline__ u64 cn_weight(int w) {
+    switch (w) {
+        case 0: return kCnWeight[0];
+        case 1: return kCnWeight[1];
+        case 2: return kCnWeight[2];
+        case 3: return kCnWeight[3];
+        case 4: return kCnWeight[4];
+        case 5: return kCnWeight[5];
+        default: return kCnWeight[6];
+    }
+}
+
+// bytes of the parts of a workgroup's LDS, in this order
+struct CnLds {
+    size_t state, hist, pat, off, nbr;
+    __host__ __device__ size_t total() const { return state + hist + pat + off + nbr; }
+};
+
+__host__ __device__ inline CnLds cn_lds(int64_t n) {
+    CnLds L;
+    L.state = (size_t)2 * n * 64 * sizeof(u64);                      // two levels [node][lane]
+    L.hist = (size_t)(CN_MAXT + 1) * (n + 2) * sizeof(u64);          // counts and witness keys of the workgroup
+    L.pat = (size_t)n * sizeof(u64);                                 // level-0 patterns of the nodes
+    L.off = ((size_t)(n + 1) * sizeof(uint16_t) + 7) / 8 * 8;        // row offsets
+    L.nbr = ((size_t)n * CN_MAXDEG + 7) / 8 * 8;                     // neighbour indices, a byte each
+    return L;
+}
+
+// The accessors copy the adjacency into LDS (off[v] .. off[v+1] of nbr) with
+// every entry checked; all 64 lanes call, the result is wave-uniform: 0 or
+// the flag bits.  Nothing is read or written out of bounds either way.
+struct CnEll {
+    const int32_t* adj;
+    int d;
+    __device__ __forceinline__ int fixed() const { return d; }
+    __device__ int load(int n, uint16_t* off, uint8_t* nbr) const {
+        const int lane = threadIdx.x;
+        bool bad = false;
+        for (int v = lane; v <= n; v += 64) off[v] = (uint16_t)(v * d);
+        for (int i = lane; i < n * d; i += 64) {
+            const int32_t u = adj[i];
+            bad |= u < 0 || u >= n;
+            nbr[i] = (uint8_t)u;
+        }
+        return __ballot(bad) ? CN_FLAG_RANGE : 0;
+    }
+};
+
+struct CnCsr {
+    const int64_t* row_ptr;
+    const int32_t* col;
+    __device__ __forceinline__ int fixed() const { return 0; }
+    __device__ int load(int n, uint16_t* off, uint8_t* nbr) const {
+        const int lane = threadIdx.x;                                // n + 1 <= 49 row pointers: a lane each
+        const int64_t base = row_ptr[0];
+        const int64_t mine = row_ptr[lane <= n ? lane : n] - base;
+        const int64_t next = row_ptr[lane < n ? lane + 1 : n] - base;
+        const bool bad_row = base != 0 || (lane < n && (next < mine || next - mine > CN_MAXDEG));
+        if (__ballot(bad_row)) return CN_FLAG_ROW;
+        if (lane <= n) off[lane] = (uint16_t)mine;                   // <= n * CN_MAXDEG
+        const int total = (int)(row_ptr[n] - base);
+        bool bad = false;
+        for (int i = lane; i < total; i += 64) {
+            const int32_t u = col[base + i];
+            bad |= u < 0 || u >= n;
+            nbr[i] = (uint8_t)u;
+        }
+        return __ballot(bad) ? CN_FLAG_RANGE : 0;
+    }
+};
+
+// level-0 pattern of node u: bit j set iff bit u of j is (u < 6); 0 for the nodes a block index decides
+__device__ __forceinline__ u64 cn_pattern(int u) {
+    const u64 pat[6] = {0xAAAAAAAAAAAAAAAAull, 0xCCCCCCCCCCCCCCCCull, 0xF0F0F0F0F0F0F0F0ull,
+                        0xFF00FF00FF00FF00ull, 0xFFFF0000FFFF0000ull, 0xFFFFFFFF00000000ull};
+    u64 x = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) x = (u == k) ? pat[k] : x;
+    return x;
+}
+
+__device__ __forceinline__ u64 cn_min64(u64 x) {
+    for (int off = 32; off; off >>= 1) {
+        const u64 o = (u64)__shfl_xor((long long)x, off);
+        x = o < x ? o : x;
+    }
+    return x;
+}
+
+// One sweep: level lv (>= 1) of the lane's block from level lv-1.  FIRST: the
+// source is level 0, generated from b and the pattern table `src` (n words;
+// b < 2^42, so bit (u + 58) mod 64 of b is bit u-6 for u >= 6 and 0 below);
+// else the LDS buffer `src`.  Wave-uniform
+// control flow (v, the row and its entries are the same in every lane).
+template <bool FIRST>
+__device__ __forceinline__ u64 cn_sweep(int n, int fixed, const uint16_t* __restrict__ off,
+                                        const uint8_t* __restrict__ nbr, const u64* __restrict__ src,
+                                        u64* __restrict__ dst, u64 b, int lane) {
+    auto word = [&](int u) -> u64 {
+        return FIRST ? (src[u] | (0 - ((b >> ((u + 58) & 63)) & 1))) : src[u * 64 + lane];
+    };
+    u64 all = ~0ull;
+    // the regular degrees: eight nodes' reads in flight together (a lone wave per SIMD waits for every
+    // LDS round trip it does not overlap), src and dst are the two different buffers
+    if (fixed == 3) {
+#pragma unroll 8
+        for (int v = 0; v < n; ++v) {
+            const uint8_t* row = nbr + 3 * v;
+            const u64 x[3] = {word(row[0]), word(row[1]), word(row[2])};
+            const u64 nw = majority_fixed<3>(x, 0);
+            dst[v * 64 + lane] = nw;
+            all &= nw;
+        }
+    } else if (fixed == 4) {
+#pragma unroll 8
+        for (int v = 0; v < n; ++v) {
+            const uint8_t* row = nbr + 4 * v;
+            const u64 x[4] = {word(row[0]), word(row[1]), word(row[2]), word(row[3])};
+            const u64 nw = majority_fixed<4>(x, word(v));
+            dst[v * 64 + lane] = nw;
+            all &= nw;
+        }
+    } else {
+        for (int v = 0; v < n; ++v) {
+            const int e0 = off[v], e1 = off[v + 1];
+            BitCounter<6> bc;                                        // degree <= 47; degree 0 keeps the word
+            bc.reset();
+            for (int e = e0; e < e1; ++e) bc.add(word(nbr[e]));
+            const u64 nw = bc.majority(e1 - e0, word(v));
+            dst[v * 64 + lane] = nw;
+            all &= nw;
+        }
+    }
+    return all;
+}
+
+template <class Adj>
+__global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo, u64 block_hi,
+                                               u64* __restrict__ counts, u64* __restrict__ witness,
+                                               int32_t* __restrict__ flag) {
+    extern __shared__ __align__(8) unsigned char cn_smem[];
+    const CnLds L = cn_lds(n);
+    u64* buf = (u64*)cn_smem;
+    u64* hist = (u64*)(cn_smem + L.state);
+    u64* pat = (u64*)(cn_smem + L.state + L.hist);
+    uint16_t* off = (uint16_t*)(cn_smem + L.state + L.hist + L.pat);
+    uint8_t* nbr = cn_smem + L.state + L.hist + L.pat + L.off;
+    const int lane = threadIdx.x;
+    const int cells = (T + 1) * (n + 1);
+    u64* best = hist + (CN_MAXT + 1) * (n + 1);                      // smallest key of level t in this workgroup
+
+    const int bad = A.load(n, off, nbr);
+    if (bad) {                                                       // wave-uniform
+        if (lane == 0) atomicOr(flag, bad);
+        return;
+    }
+    for (int i = lane; i < cells; i += 64) hist[i] = 0;
+    if (lane <= CN_MAXT) best[lane] = ~0ull;
+    if (lane < n) pat[lane] = cn_pattern(lane);
+    __syncthreads();
+
+    const int fixed = A.fixed();
+    const u64 valid = n < 6 ? ((1ull << (1 << n)) - 1) : ~0ull;      // n < 6: 2^n configurations in block 0
+    // level 0: all +1 is the last configuration of the last block
+    const u64 last_block = n > 6 ? (1ull << (n - 6)) - 1 : 0;
+    const u64 last_bit = 1ull << ((n < 6 ? (1 << n) : 64) - 1);
+    const u64 stride = (u64)gridDim.x * 64;
+    for (u64 first = block_lo + (u64)blockIdx.x * 64; first < block_hi; first += stride) {
+        const u64 b = first + lane;
+        const bool active = b < block_hi;
+        const int kb = __popcll(b);                                  // weight of the nodes >= 6
+        u64 mask = (active && b == last_block) ? last_bit : 0;
+#pragma unroll 1
+        for (int t = 0; t <= T; ++t) {
+            // a full block stays full (all +1 is a fixed point): sweep only while some lane's is not
+            if (t > 0 && __ballot(active && mask != valid)) {
+                u64* dst = buf + (size_t)((t - 1) & 1) * n * 64;
+                const u64* src = buf + (size_t)(t & 1) * n * 64;
+                const u64 all = (t == 1) ? cn_sweep<true>(n, fixed, off, nbr, pat, dst, b, lane)
+                                         : cn_sweep<false>(n, fixed, off, nbr, src, dst, b, lane);
+                mask = active ? (all & valid) : 0;
+            }
+            if (__ballot(mask != 0) == 0) continue;
+            u64 key = ~0ull;                                         // of the first weight that has a configuration
+#pragma unroll
+            for (int w = 6; w >= 0; --w) {
+                const u64 m = mask & cn_weight(w);
+                if (m) {
+                    atomicAdd(&hist[t * (n + 1) + kb + w], (u64)__popcll(m));
+                    key = ((u64)(kb + w) << 48) | (b * 64 + (u64)__builtin_ctzll(m));
+                }
+            }
+            key = cn_min64(key);
+            if (lane == 0) atomicMin(&best[t], key);
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < cells; i += 64)
+        if (hist[i]) atomicAdd(&counts[i], hist[i]);
+    if (lane <= T && best[lane] != ~0ull) atomicMin(&witness[lane], best[lane]);
+}
+
+template <class Adj>
+static int census_run(Adj A, int64_t n, int p, int c, int64_t block_lo, int64_t block_hi, int grid,
+                      unsigned long long* counts, unsigned long long* witness_key, int32_t* flag, void* stream) {
+    if (p < 0 || c < 0 || p + c - 1 < 0 || n < 1 || !counts || !witness_key || !flag || grid < 0) return MJX_EINVAL;
+    if (n > CN_MAXN || p + c - 1 > CN_MAXT) return MJX_ERANGE;
+    const int64_t B = (int64_t)1 << (n > 6 ? n - 6 : 0);
+    if (block_lo < 0 || block_lo > block_hi || block_hi > B) return MJX_EINVAL;
+    if (block_lo == block_hi) return MJX_OK;
+    const size_t lds = cn_lds(n).total();
+    // the library's grid: the workgroups the LDS lets a CU hold at once (at most 8 a SIMD), every lane
+    // walking its share of the range
+    int g = grid;
+    if (!g) {
+        const int64_t per = std::min<int64_t>(32, (int64_t)(kCnLdsPerCu / lds));
+        g = (int)std::max<int64_t>(1, std::min<int64_t>((block_hi - block_lo + 63) / 64, device_cus() * per));
+    }
+    k_census<Adj><<<(unsigned)g, 64, lds, as_stream(stream)>>>(A, (int)n, p + c - 1, (u64)block_lo, (u64)block_hi,
+                                                             counts, witness_key, flag);
+    MJX_LAUNCH_CHECK("k_census");
+    return MJX_OK;
+}
+
+}  // namespace mjx
+
+using namespace mjx;
+
+extern "C" int64_t mjx_census_lds(int64_t n) {
+    if (n < 1 || n > CN_MAXN) return -1;
+    const size_t b = cn_lds(n).total();
+    return b > kCnLdsMax ? -1 : (int64_t)b;
+}
+
+extern "C" int mjx_census_ell(const int32_t* adj, int64_t n, int d, int p, int c, int64_t block_lo, int64_t block_hi,
+                              int grid, unsigned long long* counts, unsigned long long* witness_key, int32_t* flag,
+                              void* stream) {
+    if (d < 0 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (d > CN_MAXDEG) return MJX_ERANGE;
+    return census_run(CnEll{adj, d}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, stream);
+}
+
+extern "C" int mjx_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t block_lo,
+                              int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
+                              int32_t* flag, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
+    return census_run(CnCsr{row_ptr, col}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, stream);
+}
