@@ -832,6 +832,64 @@ int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int
                       int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr, uint8_t* consensus,
                       int64_t* flipped, void* stream);
 
+/* ---- the quench in rounds: region-parallel commits ------------------------ */
+/*
+ * The pass of mjx_quench_*_rp (definitions, levels, caps, lds_entries and the
+ * overflow word of `scratch` as above) with the same result, bit for bit, by
+ * the distance-2T rule.  Trying candidate i (the light cone of its flip)
+ *   writes level l only within distance l of i, and only l <= T-1: an
+ *     accepted replica has no level-T difference;
+ *   reads level l only within distance l+2 of i (the changed nodes of level
+ *     l, their rows, and the rows of those).
+ * The adjacency is symmetric, so two candidates at graph distance > 2T have
+ * disjoint read and write sets at every level: they commute, and either may
+ * run first or both at once.  dist(i, j) <= 2T exactly when the radius-T balls
+ * of i and j meet.
+ *
+ * cand[ncand]: device int32, the nodes with a removable bit in ANY word column
+ * in `order` order (candidate k has rank k); removable: the initial mask of
+ * mjx_flip_gain_* (n * W words) -- a (candidate, column) pair whose word of it
+ * is 0 is not tried, as the sequential pass does not visit it.  A window of
+ * `window` slots holds the pending candidates of lowest rank; everything of
+ * lower rank is committed.  A round is three launches: every slot writes
+ * (round, rank) with an atomic max into a per-node claim array over its
+ * radius-T ball (de-duplicated, at most caps[T] nodes, walked once per
+ * candidate; a later round's key beats every earlier one, nothing is reset);
+ * a slot that reads its own key back on the whole ball holds the lowest rank
+ * there, is ready, and hands its slot to the next candidate; a wave per (ready
+ * candidate, word column) commits as mjx_quench_* does and adds to flipped
+ * with integer atomics.  The pending candidate of lowest rank is always ready,
+ * so ncand rounds always suffice and window = 1 is the sequential order.
+ * Stream order between launches is the only synchronisation.
+ *
+ * One call with round0 = 0 initialises (consensus[R], flipped[64 W] zeroed,
+ * the state in `scratch`, stats) and enqueues `rounds` rounds; later calls
+ * with round0 = the rounds enqueued so far and the SAME other arguments
+ * enqueue more.  Rounds enqueued after the end find nothing pending.  stats:
+ * device int64 [4], read by the caller between calls: [0] candidates left,
+ * [1] rounds that committed something, [2] the most candidates committed in
+ * one round, [3] internal.  _scratch_bytes: -1 on bad arguments; it grows with
+ * the window (the grid of the commit kernel is min(window * W, 8192)
+ * workgroups, each with its lists, plus window * (3 + caps[T]) * 4 bytes of
+ * slots and 8 n bytes of claims).
+ * MJX_EINVAL: T outside 0..6, n < 1 or n >= 2^31, R < 1, window < 1, ncand
+ * outside 0..n, round0 < 0, rounds < 0, a NULL required pointer (cand may be
+ * NULL when ncand = 0), scratch_bytes below _scratch_bytes.  No allocation, no
+ * host synchronisation.
+ */
+int64_t mjx_quench_regions_scratch_bytes(int64_t n, int64_t R, int T, const int64_t* caps, int lds_entries,
+                                         int64_t window);
+int mjx_quench_regions_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c, uint64_t* const* levels,
+                              const int64_t* caps, int lds_entries, void* scratch, int64_t scratch_bytes,
+                              int64_t window, const uint64_t* removable, const int32_t* cand, int64_t ncand,
+                              uint8_t* consensus, int64_t* flipped, int64_t* stats, int64_t round0, int64_t rounds,
+                              void* stream);
+int mjx_quench_regions_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                              uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                              int64_t scratch_bytes, int64_t window, const uint64_t* removable, const int32_t* cand,
+                              int64_t ncand, uint8_t* consensus, int64_t* flipped, int64_t* stats, int64_t round0,
+                              int64_t rounds, void* stream);
+
 /* ---- the quench as independent jobs, state in LDS ------------------------- */
 /*
  * The same pass (definitions above) for R starts x K restarts: job r*K + k

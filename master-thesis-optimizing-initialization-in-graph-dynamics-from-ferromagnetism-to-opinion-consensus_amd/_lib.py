@@ -144,6 +144,11 @@ SIGNATURES = {
                           c_vp, c_vp, c_vp],
     "mjx_quench_csr_rp": [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_vp, c_vp,
                           c_vp, c_vp, c_vp],
+    "mjx_quench_regions_scratch_bytes": [c_i64, c_i64, c_int, c_vp, c_int, c_i64],
+    "mjx_quench_regions_ell_rp": [c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_i64,
+                                  c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp],
+    "mjx_quench_regions_csr_rp": [c_vp, c_vp, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_i64, c_i64,
+                                  c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp],
     "mjx_quench_jobs_lds": [c_i64, c_int, c_vp],
     "mjx_quench_jobs_ell": [c_vp, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_vp,
                             c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -159,7 +164,8 @@ _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "
              "mjx_mt_jump_table_words": c_i64, "mjx_sa_csr_ball_work_bytes": c_i64,
              "mjx_sa_csr_lightcone_lds": c_i64, "mjx_sa_csr_lightcone_scratch_bytes": c_i64,
              "mjx_quench_lds": c_i64, "mjx_flip_gain_scratch_bytes": c_i64, "mjx_quench_scratch_bytes": c_i64,
-             "mjx_quench_jobs_lds": c_i64, "mjx_census_lds": c_i64}
+             "mjx_quench_regions_scratch_bytes": c_i64, "mjx_quench_jobs_lds": c_i64,
+             "mjx_census_lds": c_i64}
 
 MJX_OK, MJX_EINVAL, MJX_EHIP, MJX_ERANGE = 0, 1, 2, 3      # status codes (include/mjx.h)
 MJX_I8, MJX_I32, MJX_I64 = 1, 4, 8

@@ -28,7 +28,8 @@ and write its np.savez keys.
         (with ``--order-seed``): best of K orders per replica, all (replica,
         order) jobs in one call (quench.quench_restarts), a graph per replica
         for ``graphs`` files; the same keys for the best restart plus
-        mag_restarts (R, K) and best
+        mag_restarts (R, K) and best.  ``--schedule regions [--window K]``:
+        the single pass in rounds (same output; quench.quench's schedule)
   census  no reference script: the exact consensus census (census.census) of
         one small random regular or Erdos-Renyi graph (n <= 48, isolated nodes
         kept), every one of the 2^n starts run p + c - 1 steps; output
@@ -114,6 +115,10 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--restarts must be >= 0")
             if a.restarts >= 1 and a.order_seed is None:
                 self.error("--restarts K needs --order-seed: the K orders are drawn from it")
+            if a.window is not None and (a.schedule != "regions" or a.window < 1):
+                self.error("--window K (K >= 1) belongs to --schedule regions")
+            if a.schedule == "regions" and a.restarts >= 1:
+                self.error("--schedule regions is a schedule of the single pass: not with --restarts")
         return a
 
 
@@ -176,6 +181,12 @@ def build_parser():
                     help="K >= 1: best of K orders per replica in one call (quench.quench_restarts), job (r, k) "
                          "walking np.random.default_rng([S, r, k]).permutation(n) with S = --order-seed (required); "
                          "0: one pass as above")
+    qu.add_argument("--schedule", choices=("sequential", "regions"), default="sequential",
+                    help="of the single pass (--restarts 0): regions commits candidates whose balls do not meet in "
+                         "the same round; same output, faster on large graphs")
+    qu.add_argument("--window", type=int, default=None,
+                    help="--schedule regions: pending candidates that compete per round (default: from n and the "
+                         "ball bound)")
     qu.add_argument("--out", default=None, help="output .npz (default: the input's name + _quenched)")
     ce = sub.add_parser("census", help="count the starts of a small graph that reach consensus, all 2^n of them "
                                        "(no reference script)")
@@ -357,6 +368,7 @@ def run_quench(a):
     S = conf.astype(np.int64)                   # the result files hold +-1 as floats
     if "graphs" in res and res["graphs"].shape[0] != S.shape[0]:
         raise SystemExit(f"{a.inp}: {res['graphs'].shape[0]} graphs for {S.shape[0]} configurations")
+    how = {"schedule": a.schedule, "window": a.window} if a.schedule != "sequential" else {}
     if a.restarts >= 1:
         # best of K orders per replica, every (replica, order) a job of one call; SA / HPR files: the
         # (R, n, d) stack, a graph per replica
@@ -368,11 +380,11 @@ def run_quench(a):
         res["mag_restarts"], res["best"] = qr["mag"], qr["best"]
     elif "graphs" in res:
         # one graph per replica (code/SA_RRG.py:58-62): replica by replica
-        runs = [quench(res["graphs"][k].astype(np.int32), S[k:k + 1], a.p, a.c, seed=a.order_seed)
+        runs = [quench(res["graphs"][k].astype(np.int32), S[k:k + 1], a.p, a.c, seed=a.order_seed, **how)
                 for k in range(S.shape[0])]
         q = {k: np.concatenate([r[k] for r in runs]) for k in ("conf", "mag", "flipped", "consensus")}
     else:
-        q = quench(Graph.csr(res["row_ptr"], res["col"]), S, a.p, a.c, seed=a.order_seed)
+        q = quench(Graph.csr(res["row_ptr"], res["col"]), S, a.p, a.c, seed=a.order_seed, **how)
     res["conf_quenched"] = q["conf"].astype(conf.dtype)
     res["mag_quenched"], res["flipped"], res["consensus"] = q["mag"], q["flipped"], q["consensus"]
     out = a.out or (a.inp[:-4] if a.inp.endswith(".npz") else a.inp) + "_quenched.npz"

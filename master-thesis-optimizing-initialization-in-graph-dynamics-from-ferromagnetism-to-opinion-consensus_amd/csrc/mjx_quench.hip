@@ -1,7 +1,8 @@
 // Flip gains and the greedy quench (no reference counterpart; definitions in
 // include/mjx.h): for every node i and replica r the change of F(s) = sum of
 // onestep^T(s) when spin i alone is flipped, the mask of +1 spins a consensus
-// replica can drop, and the sequential zero-temperature pass that drops them.
+// replica can drop, and the zero-temperature pass that drops them: sequential
+// (a workgroup per word column) or in rounds of region-parallel commits.
 //
 // One evaluator serves all of it.  A wave owns one (node i, word column) pair:
 // the 64 replicas of the column are the 64 bits of every word it touches, its
@@ -338,6 +339,198 @@ __global__ void __launch_bounds__(64) k_quench(Adj A, QnCone C, int T, int64_t n
     flipped[col * 64 + lane] = mine;
 }
 
+// ---- the region-parallel pass ---------------------------------------------
+// The candidates of ALL word columns (the union, in `order` order; candidate
+// k has rank k) are committed in rounds.  Trying candidate i writes level l
+// within distance l of i (l <= T-1; an accepted replica has no level-T diff)
+// and reads it within distance l+2, so two candidates further apart than 2T
+// have disjoint read and write sets and commute: both may run in the same
+// round, on different workgroups.  dist(i, j) <= 2T exactly when the radius-T
+// balls of i and j meet.  A window of K slots holds the K pending candidates of
+// lowest rank.  Per round (three launches; stream order is the only
+// synchronisation between workgroups):
+//   reserve  every slot writes its key into claim[v] for every node v of its
+//            ball with an atomic max.  key = (round + 1) << 32 | ~rank: within
+//            a round the lowest rank wins, and a key of an earlier round never
+//            survives a later one, so nothing is reset;
+//   check    a slot that reads its own key back on its whole ball has no
+//            pending candidate of lower rank within 2T: its node goes to the
+//            ready list and the slot takes the next candidate (an atomic
+//            cursor into the order) and walks its ball, once per candidate;
+//   commit   a wave per (ready node, word column) runs k_quench's body.
+// The pending candidate of lowest rank always wins its ball, so a round with
+// anything pending commits at least one candidate.
+struct QrState {
+    unsigned long long* stats;    // caller's [4]: candidates left, rounds that committed, most commits of a
+                                  // round, cursor (the next rank to hand out; it runs on past the end)
+    unsigned long long* claim;    // [n] keys
+    int32_t* nready;              // [1] entries of `ready`
+    int32_t* rank;                // [K] rank of the slot's candidate, -1: empty
+    int32_t* bcnt;                // [K] nodes of its ball
+    int32_t* ready;               // [K] the nodes that commit in this round
+    int32_t* ball;                // [K][capB] the balls, each node once
+    int capB;                     // caps[T]
+    int K;
+};
+
+__device__ __forceinline__ unsigned long long qr_key(long long round, int32_t rank) {
+    return ((unsigned long long)(round + 1) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)rank);
+}
+
+// The nodes within distance T of i, each once, into ball[0 .. cap): the cone's
+// candidate walk (a lane per frontier node, the lanes walking their rows
+// together) without the words.  Returns the count; ok = false when the ball
+// outgrew cap or a row names a node >= n (nothing is written out of bounds, the
+// ball is then incomplete).  One wave = the workgroup; wave-uniform control flow.
+template <class Adj>
+__device__ int qr_ball(const Adj& A, int T, int64_t n, uint32_t i, int32_t* ball, int cap, bool& ok) {
+    const int lane = threadIdx.x;
+    const u64 below = (1ull << lane) - 1;
+    if (lane == 0) ball[0] = (int32_t)i;
+    __syncthreads();
+    int nu = 1, f0 = 0;
+    for (int lv = 1; lv <= T && ok; ++lv) {
+        const int f1 = nu;
+        for (int base = f0; base < f1 && ok; base += 64) {
+            const bool have = base + lane < f1;
+            const uint32_t v = have ? (uint32_t)ball[base + lane] : 0u;
+            const int dg = have ? A.deg(v) : 0;
+            int longest = dg;
+            for (int off = 32; off; off >>= 1) {
+                const int o = __shfl_xor(longest, off);
+                longest = o > longest ? o : longest;
+            }
+            const int lanes = (f1 - base) < 64 ? (f1 - base) : 64;
+            for (int e = 0; e < longest && ok; ++e) {
+                const bool valid = e < dg;
+                const uint32_t x = valid ? A.nbr(v, e) : kQnNoNode;
+                if (__ballot(valid && x >= (uint32_t)n)) { ok = false; break; }
+                u64 seen = 0;
+                for (int m = 0; m < lanes; ++m) {
+                    const uint32_t y = qn_lane32(x, m);
+                    if (__ballot(x == y) & ((1ull << m) - 1)) seen |= 1ull << m;
+                }
+                for (int b = 0; b < nu; b += 64) {
+                    const uint32_t have_c = (b + lane < nu) ? (uint32_t)ball[b + lane] : 0xfffffffeu;
+                    for (int m = 0; m < lanes; ++m) {
+                        const uint32_t y = qn_lane32(x, m);
+                        if (__ballot(have_c == y)) seen |= 1ull << m;
+                    }
+                }
+                const bool fresh = valid && !((seen >> lane) & 1);
+                const u64 mask = __ballot(fresh);
+                const int pos = nu + __popcll(mask & below);
+                const int total = nu + __popcll(mask);
+                if (total > cap) ok = false;
+                else if (fresh) ball[pos] = (int32_t)x;
+                nu = ok ? total : nu;
+                __syncthreads();
+            }
+        }
+        f0 = f1;
+    }
+    return nu;
+}
+
+__global__ void __launch_bounds__(64) k_qr_init(QrState Q, int64_t ncand) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t < Q.K) Q.rank[t] = -1;
+    if (t == 0) {
+        Q.stats[0] = (unsigned long long)ncand;
+        Q.stats[1] = Q.stats[2] = Q.stats[3] = 0;
+        *Q.nready = 0;
+    }
+}
+
+__global__ void __launch_bounds__(64) k_qr_reserve(QrState Q, long long round) {
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    if (slot == 0 && lane == 0) *Q.nready = 0;              // the ready list of the round before is spent
+    const int32_t rk = Q.rank[slot];
+    if (rk < 0) return;
+    const unsigned long long key = qr_key(round, rk);
+    const int32_t* ball = Q.ball + (int64_t)slot * Q.capB;
+    const int cnt = Q.bcnt[slot];
+    for (int q = lane; q < cnt; q += 64) atomicMax(&Q.claim[ball[q]], key);
+}
+
+// round < 0: the first fill, nothing to check
+template <class Adj>
+__global__ void __launch_bounds__(64) k_qr_check(Adj A, QrState Q, int T, int64_t n, const int32_t* __restrict__ cand,
+                                                 int64_t ncand, long long round, u64* __restrict__ flag) {
+    const int slot = blockIdx.x, lane = threadIdx.x;
+    int32_t* ball = Q.ball + (int64_t)slot * Q.capB;
+    const int32_t rk = Q.rank[slot];
+    if (rk >= 0) {
+        const unsigned long long key = qr_key(round, rk);
+        const int cnt = Q.bcnt[slot];
+        bool lost = false;
+        for (int q = lane; q < cnt; q += 64) lost |= Q.claim[ball[q]] != key;
+        if (__ballot(lost)) return;                          // a pending candidate of lower rank within 2T: wait
+        if (lane == 0) Q.ready[atomicAdd(Q.nready, 1)] = cand[rk];
+    }
+    // the slot is free: the next candidate of the order and its ball
+    unsigned long long nx = 0;
+    if (lane == 0) nx = atomicAdd(&Q.stats[3], 1ull);
+    nx = qn_lane64(nx, 0);
+    if (nx >= (unsigned long long)ncand) {
+        if (lane == 0) Q.rank[slot] = -1;
+        return;
+    }
+    bool ok = true;
+    const int cnt = qr_ball(A, T, n, (uint32_t)cand[nx], ball, Q.capB, ok);
+    if (lane == 0) {
+        Q.rank[slot] = (int32_t)nx;
+        Q.bcnt[slot] = cnt;
+        if (!ok) *flag = 1;
+    }
+}
+
+// k_quench's body for every (ready node, word column) pair.  The ready nodes
+// are further apart than 2T, so no pair reads a word another pair writes.
+template <class Adj>
+__global__ void __launch_bounds__(64) k_qr_commit(Adj A, QnCone C, QrState Q, int T, int64_t n, int64_t W, int64_t R,
+                                                  const u64* __restrict__ removable,
+                                                  unsigned long long* __restrict__ flipped) {
+    extern __shared__ __align__(8) unsigned char qn_lds[];
+    const QnLists S = qn_lists(C, T, qn_lds, blockIdx.x);
+    const int lane = threadIdx.x;
+    const int nr = *Q.nready;
+    if (blockIdx.x == 0 && lane == 0 && nr > 0) {
+        Q.stats[0] -= (unsigned long long)nr;
+        Q.stats[1] += 1;
+        if ((unsigned long long)nr > Q.stats[2]) Q.stats[2] = (unsigned long long)nr;
+    }
+    int cnt[QN_MAXT + 1];
+    const int64_t pairs = (int64_t)nr * W;
+    for (int64_t pid = blockIdx.x; pid < pairs; pid += gridDim.x) {
+        const int64_t q = pid / W, col = pid - q * W;
+        const uint32_t i = (uint32_t)Q.ready[q];
+        if (removable[(int64_t)i * W + col] == 0) continue;  // no candidate of this column: the pass skips it
+        const u64 cons = C.header[1 + 64 * W + col] & qn_valid(col, W, R);
+        const u64 d0 = C.L[0][(int64_t)i * W + col] & cons;
+        if (d0 == 0) continue;
+        const bool ok = qn_cone(A, C, S, T, W, col, i, d0, cnt);
+        if (!ok) {
+            if (lane == 0) C.header[0] = 1;
+            __syncthreads();
+            continue;
+        }
+        u64 orT = 0;
+        for (int k = lane; k < cnt[T]; k += 64) orT |= S.diff(T, k);
+        for (int off = 32; off; off >>= 1) orT |= (u64)__shfl_xor((long long)orT, off);
+        const u64 acc = d0 & ~orT;
+        if (acc) {
+            for (int l = 0; l <= T; ++l)
+                for (int k = lane; k < cnt[l]; k += 64) {
+                    const u64 dq = S.diff(l, k) & acc;
+                    if (dq) C.L[l][(int64_t)S.node(l, k) * W + col] ^= dq;
+                }
+            if ((acc >> lane) & 1) atomicAdd(&flipped[col * 64 + lane], 1ull);
+        }
+        __syncthreads();                                     // the lists are reused by the next pair
+    }
+}
+
 // list capacities, LDS part and scratch slots from the caps (HOST int64 [T+1])
 static int qn_plan(int T, const int64_t* caps, int lds_entries, QnCone& C) {
     if (T < 0 || T > QN_MAXT || !caps || lds_entries < 0) return MJX_EINVAL;
@@ -431,6 +624,71 @@ static int quench_run(Adj A, int64_t n, int64_t R, int p, int c, uint64_t* const
     return MJX_OK;
 }
 
+// region-parallel pass: workgroups of the commit kernel, and the scratch behind
+// the header: their lists, then claim[n], nready (8 bytes), rank, bcnt, ready
+// [K] and ball[K][caps[T]]
+static int64_t qr_commit_blocks(int64_t K, int64_t W) { return std::min<int64_t>(K * W, kQnMaxBlocks); }
+
+static int64_t qr_state_bytes(int64_t n, int64_t K, int64_t capB) {
+    return 8 * n + 8 + ((4 * K * (3 + capB) + 7) / 8) * 8;
+}
+
+static bool qr_shape_ok(int64_t n, int64_t R, int64_t window) {
+    return n >= 1 && n <= (int64_t)INT32_MAX && R >= 1 && (R + 63) / 64 <= (int64_t)INT32_MAX && window >= 1 &&
+           window <= (int64_t)INT32_MAX;
+}
+
+template <class Adj>
+static int quench_regions_run(Adj A, int64_t n, int64_t R, int p, int c, uint64_t* const* levels, const int64_t* caps,
+                              int lds_entries, void* scratch, int64_t scratch_bytes, int64_t window,
+                              const uint64_t* removable, const int32_t* cand, int64_t ncand, uint8_t* consensus,
+                              int64_t* flipped, int64_t* stats, int64_t round0, int64_t rounds, void* stream) {
+    if (!removable || !consensus || !flipped || !stats || !qr_shape_ok(n, R, window) || ncand < 0 || ncand > n ||
+        (ncand > 0 && !cand) || round0 < 0 || rounds < 0 || round0 + rounds > (int64_t)INT32_MAX)
+        return MJX_EINVAL;
+    const int64_t W = (R + 63) / 64, K = window;
+    const int64_t blocks = qr_commit_blocks(K, W);
+    QnCone C;
+    if (int rc = qn_setup(n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, blocks, C)) return rc;
+    const int T = p + c - 1;
+    const int64_t capB = C.cap[T + 1];                       // caps[T]
+    if (scratch_bytes < qn_header_bytes(W) + blocks * C.stride + qr_state_bytes(n, K, capB)) return MJX_EINVAL;
+    QrState Q;
+    unsigned char* at = C.lists + blocks * C.stride;
+    Q.stats = (unsigned long long*)stats;
+    Q.claim = (unsigned long long*)at;
+    Q.nready = (int32_t*)(at + 8 * n);
+    Q.rank = (int32_t*)(at + 8 * n + 8);
+    Q.bcnt = Q.rank + K;
+    Q.ready = Q.bcnt + K;
+    Q.ball = Q.ready + K;
+    Q.capB = (int)capB;
+    Q.K = (int)K;
+    hipStream_t hs = as_stream(stream);
+    if (round0 == 0) {
+        if (int rc = qn_consensus(C, T, n, R, consensus, stream)) return rc;
+        MJX_HIP(hipMemsetAsync(flipped, 0, (size_t)(64 * W) * sizeof(int64_t), hs), "quench regions flipped memset");
+        MJX_HIP(hipMemsetAsync(Q.claim, 0, (size_t)n * 8, hs), "quench regions claim memset");
+        k_qr_init<<<(unsigned)((K + 63) / 64), 64, 0, hs>>>(Q, ncand);
+        MJX_LAUNCH_CHECK("k_qr_init");
+        if (ncand > 0) {
+            k_qr_check<Adj><<<(unsigned)K, 64, 0, hs>>>(A, Q, T, n, cand, ncand, -1, C.header);
+            MJX_LAUNCH_CHECK("k_qr_check (fill)");
+        }
+    }
+    if (ncand == 0) return MJX_OK;
+    for (int64_t r = round0; r < round0 + rounds; ++r) {
+        k_qr_reserve<<<(unsigned)K, 64, 0, hs>>>(Q, (long long)r);
+        MJX_LAUNCH_CHECK("k_qr_reserve");
+        k_qr_check<Adj><<<(unsigned)K, 64, 0, hs>>>(A, Q, T, n, cand, ncand, (long long)r, C.header);
+        MJX_LAUNCH_CHECK("k_qr_check");
+        k_qr_commit<Adj><<<(unsigned)blocks, 64, qn_lds_bytes(T, C.E), hs>>>(A, C, Q, T, n, W, R, (const u64*)removable,
+                                                                            (unsigned long long*)flipped);
+        MJX_LAUNCH_CHECK("k_qr_commit");
+    }
+    return MJX_OK;
+}
+
 }  // namespace mjx
 
 using namespace mjx;
@@ -500,4 +758,32 @@ extern "C" int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int
     if (!row_ptr) return MJX_EINVAL;
     return quench_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, cand,
                       cand_ptr, consensus, flipped, stream);
+}
+
+extern "C" int64_t mjx_quench_regions_scratch_bytes(int64_t n, int64_t R, int T, const int64_t* caps, int lds_entries,
+                                                    int64_t window) {
+    QnCone C;
+    if (!qr_shape_ok(n, R, window) || qn_plan(T, caps, lds_entries, C)) return -1;
+    const int64_t W = (R + 63) / 64;
+    return qn_header_bytes(W) + qr_commit_blocks(window, W) * C.stride + qr_state_bytes(n, window, C.cap[T + 1]);
+}
+
+extern "C" int mjx_quench_regions_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R, int p, int c,
+                                         uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                                         int64_t scratch_bytes, int64_t window, const uint64_t* removable,
+                                         const int32_t* cand, int64_t ncand, uint8_t* consensus, int64_t* flipped,
+                                         int64_t* stats, int64_t round0, int64_t rounds, void* stream) {
+    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    return quench_regions_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, window,
+                              removable, cand, ncand, consensus, flipped, stats, round0, rounds, stream);
+}
+
+extern "C" int mjx_quench_regions_csr_rp(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int p, int c,
+                                         uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
+                                         int64_t scratch_bytes, int64_t window, const uint64_t* removable,
+                                         const int32_t* cand, int64_t ncand, uint8_t* consensus, int64_t* flipped,
+                                         int64_t* stats, int64_t round0, int64_t rounds, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;
+    return quench_regions_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes,
+                              window, removable, cand, ncand, consensus, flipped, stats, round0, rounds, stream);
 }

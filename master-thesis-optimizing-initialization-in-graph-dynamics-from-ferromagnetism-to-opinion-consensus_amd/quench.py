@@ -15,7 +15,10 @@ onestep^t(s), t = 0..T (one ``rollout`` step per level); ``quench`` walks, per
 word column, the nodes of the initial removable mask in ``order`` order with
 the same evaluator and commits the accepted flips into copies of the levels.
 SA and HPR stop at the first configuration that reaches consensus; this is the
-zero-temperature clean-up after them.
+zero-temperature clean-up after them.  ``quench(..., schedule="regions")`` is
+the same pass in rounds: candidates further apart than 2 (p + c - 1) commute,
+so those of a window whose balls meet no ball of an earlier pending candidate
+commit together, for all word columns at once; the result is identical.
 
 The local minimum depends on the visiting order.  ``quench_restarts`` runs
 R starts x K orders as R K independent jobs in one call
@@ -244,14 +247,107 @@ def _quench_pass(g, levels, R, W, p, c, T, caps, cand, cand_ptr, lds_entries):
     return consensus, flipped[:R]
 
 
-def _quench_packed(g, bits, R, W, p, c, T, order, lds_entries):
-    """-> (state = packed result (a new tensor), consensus uint8 [R], flipped int64 [R], candidates visited)."""
+def _quench_packed(g, bits, R, W, p, c, T, order, lds_entries, schedule="sequential", window=None):
+    """-> (state = packed result (a new tensor), consensus uint8 [R], flipped int64 [R], candidates visited,
+    the regions pass's {"rounds", "window", "max_commits"} or {})."""
+    if schedule == "regions":
+        caps = _caps(g, T)
+        levels = _levels(g, bits, W, T, copy=True)
+        removable, _, _ = _flip_gains_packed(g, levels, R, W, p, c, T, caps, lds_entries, False)
+        cand, visited = _union_candidates(removable, g.n, W, order)
+        consensus, flipped, info = _quench_regions_pass(g, levels, R, W, p, c, T, caps, removable, cand, window,
+                                                        lds_entries)
+        return levels[0], consensus, flipped, visited, info
     levels, caps, cand, cand_ptr = _quench_prepare(g, bits, R, W, p, c, T, order, lds_entries)
     consensus, flipped = _quench_pass(g, levels, R, W, p, c, T, caps, cand, cand_ptr, lds_entries)
-    return levels[0], consensus, flipped, int(cand.numel())
+    return levels[0], consensus, flipped, int(cand.numel()), {}
 
 
-def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, validate=True):
+SCHEDULES = ("sequential", "regions")
+WINDOW_BALLS = 16           # default window: this many times n / (estimated 2T-ball), see default_window
+WINDOW_MAX = 8192
+
+
+def _check_schedule(schedule, window):
+    """Host only -> window as an int or None."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"unknown schedule {schedule!r}: one of {SCHEDULES}")
+    if window is None:
+        return None
+    if schedule != "regions":
+        raise ValueError("window belongs to schedule='regions': the sequential pass has none")
+    if isinstance(window, bool) or int(window) != window or int(window) < 1:
+        raise ValueError(f"window must be an integer >= 1, got {window!r}")
+    return int(window)
+
+
+def default_window(n, ball_T):
+    """Slots of the regions pass when none are asked for.  Two candidates can
+    commit together when their radius-T balls (at most ``ball_T`` = caps[T]
+    nodes) do not meet, so about n / B candidates fit one round, B the 2T-ball,
+    estimated from above by min(n, ball_T^2); slots past a few times that only
+    wait.  WINDOW_BALLS of them, at least 1, at most WINDOW_MAX (the stored
+    balls, 4 ball_T bytes a slot, then stay below 64 MB for every n < 2^31)."""
+    n, ball_T = int(n), max(1, int(ball_T))
+    return int(max(1, min(WINDOW_BALLS * n // min(n, ball_T * ball_T), WINDOW_MAX)))
+
+
+def _union_candidates(removable, n, W, order):
+    """The nodes with a removable bit in any word column, in ``order`` order
+    (int32 on the device), and the (node, column) pairs the pass visits."""
+    rem = removable.view(n, W) != 0
+    visited = int(rem.sum().item())
+    some = rem.any(dim=1)
+    if order is None:
+        cand = some.nonzero()[:, 0]
+    else:
+        order_t = torch.from_numpy(order).to(removable.device)
+        cand = order_t[some[order_t].nonzero()[:, 0]]
+    return cand.to(torch.int32).contiguous(), visited
+
+
+def _quench_regions_pass(g, levels, R, W, p, c, T, caps, removable, cand, window, lds_entries):
+    """The pass in rounds (csrc/mjx_quench.hip, the region-parallel pass):
+    ``levels`` are updated in place -> (consensus uint8 [R], flipped int64 [R],
+    {"rounds", "window", "max_commits"}).  The host reads the candidates-left
+    counter once per chunk of rounds and never enqueues more rounds than there
+    are candidates."""
+    dev = levels[0].device
+    lib = _lib.load()
+    ncand = int(cand.numel())
+    K = max(1, min(default_window(g.n, caps[T]) if window is None else window, ncand))
+    scratch = _scratch(lib.mjx_quench_regions_scratch_bytes(g.n, R, T, caps, lds_entries, K), "quench", T, lds_entries,
+                       dev)
+    lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
+    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
+    flipped = torch.empty(64 * W, dtype=torch.int64, device=dev)
+    stats = torch.empty(4, dtype=torch.int64, device=dev)
+    kind, ga = _graph_args(g)
+
+    def enqueue(round0, rounds):
+        _lib.call(f"mjx_quench_regions_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch),
+                  scratch.numel() * 8, K, _device.ptr(removable), _device.ptr(cand) if ncand else None, ncand,
+                  _device.ptr(consensus), _device.ptr(flipped), _device.ptr(stats), round0, rounds,
+                  _device.stream_handle())
+        return [int(x) for x in stats.cpu().tolist()]
+
+    launched = min(ncand, 16)
+    left, rounds, most, _ = enqueue(0, launched)
+    while left:
+        _check_overflow(scratch, "quench")
+        if launched >= ncand:
+            raise _lib.MjxError(f"quench: {left} of {ncand} candidates are left after {launched} rounds; every round "
+                                "with a pending candidate commits one")
+        # as many rounds as the commits per round so far would need, at most 1024 between two reads
+        chunk = min(ncand - launched, 1024, max(1, -(-left * rounds // max(1, ncand - left))))
+        left, rounds, most, _ = enqueue(launched, chunk)
+        launched += chunk
+    _check_overflow(scratch, "quench")
+    return consensus, flipped[:R], {"rounds": rounds, "window": K, "max_commits": most}
+
+
+def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, validate=True, schedule="sequential",
+           window=None):
     """One greedy pass: every consensus replica of ``s`` visits the nodes in
     ``order`` (a permutation of 0..n-1 shared by all replicas; default the
     identity; ``seed`` is shorthand for ``np.random.default_rng(seed)
@@ -263,9 +359,21 @@ def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, valid
     shape and kind as the input), ``state`` and ``words`` (the packed result, a
     device tensor of n * ``words`` int64: all a packed input gets back),
     ``flipped`` int64 [R], ``consensus`` bool [R] (of the input), ``mag``
-    float64 [R] = sum(s)/n of the result, ``visited`` = candidates walked."""
+    float64 [R] = sum(s)/n of the result, ``visited`` = candidates walked.
+
+    ``schedule``: ``"sequential"`` (default) walks every word column's
+    candidates one after the other, a workgroup per column.  ``"regions"``
+    gives the same result, bit for bit, in rounds: the candidates of all
+    columns share one order, and those of a window of ``window`` pending
+    candidates whose radius-(p+c-1) balls meet no ball of an earlier pending
+    candidate commit together, on as many workgroups as there are (candidate,
+    column) pairs (``window=None``: ``default_window``).  It adds ``rounds``,
+    ``window`` (the slots used: never more than there are candidates) and
+    ``max_commits`` (the most candidates of one round) to the dict.  It pays
+    on large graphs (n of 1e5 and more at T = 3, d = 4)."""
     p, c, T = _steps(p, c)
     lds_entries = _kernel_options(kernel)
+    window = _check_schedule(schedule, window)
     order = _check_order(order, seed, _host_n(graph, s, words))
     g = as_graph(graph)
     if order is not None and order.shape[0] != g.n:
@@ -273,12 +381,13 @@ def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, valid
     if validate:
         _check_symmetric(g)
     bits, R, W, ndim = _packed_input(g, s, words)
-    state, consensus, flipped, visited = _quench_packed(g, bits, R, W, p, c, T, order, lds_entries)
+    state, consensus, flipped, visited, info = _quench_packed(g, bits, R, W, p, c, T, order, lds_entries, schedule,
+                                                              window)
     plus = popcount(state, g.n, words=W)[:R]
     # sum(s) / n as numpy divides two integers (a device division may multiply by 1/n)
     mag = torch.from_numpy((2 * plus.cpu().numpy() - g.n) / g.n)
     out = {"flipped": _like(flipped, s), "consensus": _like(consensus.to(torch.bool), s), "mag": _like(mag, s),
-           "visited": visited, "state": state, "words": W}
+           "visited": visited, "state": state, "words": W, **info}
     if words is not None:
         return out
     conf = unpack(state, g.n, R)
