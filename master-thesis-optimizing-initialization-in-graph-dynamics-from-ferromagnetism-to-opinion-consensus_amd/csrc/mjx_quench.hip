@@ -20,7 +20,7 @@
 // The wave is the whole workgroup, so the lanes see each other's plain stores
 // to LDS, scratch and (quench) the levels after a workgroup barrier: one CU,
 // one vector L1.  Everything is integer; no flags needed.
-#include "mjx_common.h"
+#include "mjx_quench_parts.h"
 #include <algorithm>
 
 namespace mjx {
@@ -40,22 +40,6 @@ struct QnCone {
     int64_t stride;               // bytes of scratch per workgroup (multiple of 8)
     unsigned char* lists;         // scratch behind the header
     u64* header;                  // [0] overflow flag, [1, 1+64W) +1 counts of L_T, [1+64W, 1+65W) consensus words
-};
-
-struct AdjEll {
-    const int32_t* adj;
-    int d;
-    __device__ __forceinline__ int deg(uint32_t) const { return d; }
-    __device__ __forceinline__ uint32_t nbr(uint32_t v, int e) const { return (uint32_t)adj[(int64_t)v * d + e]; }
-    __device__ __forceinline__ int fixed() const { return d; }
-};
-
-struct AdjCsr {
-    const int64_t* row_ptr;
-    const int32_t* col;
-    __device__ __forceinline__ int deg(uint32_t v) const { return (int)(row_ptr[v + 1] - row_ptr[v]); }
-    __device__ __forceinline__ uint32_t nbr(uint32_t v, int e) const { return (uint32_t)col[row_ptr[v] + e]; }
-    __device__ __forceinline__ int fixed() const { return 0; }
 };
 
 // The lists of one workgroup (= one wave): LDS part and scratch part.
@@ -99,12 +83,6 @@ __device__ __forceinline__ QnLists qn_lists(const QnCone& C, int T, unsigned cha
     return S;
 }
 
-constexpr uint32_t kQnNoNode = 0xffffffffu;    // never a node (n < 2^31)
-
-// register of lane m (wave-uniform m)
-__device__ __forceinline__ uint32_t qn_lane32(uint32_t x, int m) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, m);
-}
 __device__ __forceinline__ u64 qn_lane64(u64 x, int m) {
     return (u64)qn_lane32((uint32_t)x, m) | ((u64)qn_lane32((uint32_t)(x >> 32), m) << 32);
 }
@@ -153,11 +131,7 @@ __device__ __forceinline__ u64 qn_new_word(const Adj& A, const QnLists& S, const
         return majority_fixed<4>(x, own);
     }
     const int dg = has ? A.deg(j) : 0;
-    int longest = dg;
-    for (int off = 32; off; off >>= 1) {
-        const int o = __shfl_xor(longest, off);
-        longest = o > longest ? o : longest;
-    }
+    const int longest = qn_wave_max(dg);
     BitCounter<8> bc;                            // degree <= 255; degree 0 keeps the word
     bc.reset();
     for (int e = 0; e < longest; ++e) bc.add(word(e < dg ? A.nbr(j, e) : kQnNoNode));   // a lane past its row adds 0
@@ -192,36 +166,13 @@ __device__ bool qn_cone(const Adj& A, const QnCone& C, const QnLists& S, int T, 
             const bool have = base + lane < np;
             const uint32_t v = have ? S.node(lv - 1, base + lane) : 0u;
             const int dg = have ? A.deg(v) : -1;
-            int longest = dg;
-            for (int off = 32; off; off >>= 1) {
-                const int o = __shfl_xor(longest, off);
-                longest = o > longest ? o : longest;
-            }
+            const int longest = qn_wave_max(dg);
             const int lanes = (np - base) < 64 ? (np - base) : 64;
             for (int e = 0; e <= longest && ok; ++e) {
                 const bool valid = e <= dg;
                 const uint32_t x = valid ? (e == 0 ? v : A.nbr(v, e - 1)) : kQnNoNode;
-                // bit m of seen: lane m's offer is a candidate already, or a lower lane offers it too
-                u64 seen = 0;
-                for (int m = 0; m < lanes; ++m) {
-                    const uint32_t y = qn_lane32(x, m);
-                    if (__ballot(x == y) & ((1ull << m) - 1)) seen |= 1ull << m;
-                }
-                for (int b = 0; b < nu; b += 64) {
-                    const uint32_t have_c = (b + lane < nu) ? S.cand(b + lane) : 0xfffffffeu;
-                    for (int m = 0; m < lanes; ++m) {
-                        const uint32_t y = qn_lane32(x, m);
-                        if (__ballot(have_c == y)) seen |= 1ull << m;
-                    }
-                }
-                const bool fresh = valid && !((seen >> lane) & 1);
-                const u64 mask = __ballot(fresh);
-                const int pos = nu + __popcll(mask & below);
-                const int total = nu + __popcll(mask);
-                if (total > C.cap[T + 1]) ok = false;
-                else if (fresh) S.put_cand(pos, x);
-                nu = ok ? total : nu;
-                __syncthreads();
+                ok = qn_offer(x, valid, lanes, nu, C.cap[T + 1], [&](int q) { return S.cand(q); },
+                              [&](int q, uint32_t y) { S.put_cand(q, y); });
             }
         }
         // recompute the candidates; keep those whose word differs from the cached level
@@ -249,6 +200,36 @@ __device__ bool qn_cone(const Adj& A, const QnCone& C, const QnLists& S, int T, 
 __device__ __forceinline__ u64 qn_valid(int64_t col, int64_t W, int64_t R) {
     const int tail = (int)(R & 63);
     return (col == W - 1 && tail) ? ((1ull << tail) - 1) : ~0ull;
+}
+
+// Try the flip {i: d0} in word column col and commit it in the replicas where
+// consensus survives it: the cone, the OR of the level-T differences, acc =
+// d0 & ~OR, the differences masked by acc XORed into every level, a barrier
+// (the commits land, and the lists are free, before the next try).  Returns
+// false on overflow: the header's flag is set, nothing is committed and acc
+// is 0.  cnt is the caller's [QN_MAXT + 1], declared once outside its loop
+// (declared here it costs 7 VGPRs and three of the four kernels an occupancy step).
+template <class Adj>
+__device__ __forceinline__ bool qn_try_commit(const Adj& A, const QnCone& C, const QnLists& S, int T, int64_t W,
+                                              int64_t col, uint32_t i, u64 d0, int* cnt, u64& acc) {
+    const int lane = threadIdx.x;
+    const bool ok = qn_cone(A, C, S, T, W, col, i, d0, cnt);
+    acc = 0;
+    if (!ok) {
+        if (lane == 0) C.header[0] = 1;
+    } else {
+        u64 orT = 0;
+        for (int q = lane; q < cnt[T]; q += 64) orT |= S.diff(T, q);
+        acc = d0 & ~qn_wave_or(orT);
+        if (acc)
+            for (int l = 0; l <= T; ++l)
+                for (int q = lane; q < cnt[l]; q += 64) {    // the nodes of a list are distinct: one lane per word
+                    const u64 dq = S.diff(l, q) & acc;
+                    if (dq) C.L[l][(int64_t)S.node(l, q) * W + col] ^= dq;
+                }
+    }
+    __syncthreads();
+    return ok;
 }
 
 // consensus[r] = (+1 count of L_T == n), and the same as a word per column
@@ -317,24 +298,9 @@ __global__ void __launch_bounds__(64) k_quench(Adj A, QnCone C, int T, int64_t n
         // the flip is tried in the replicas where it can count: s_i = +1 and consensus
         const u64 d0 = C.L[0][(int64_t)i * W + col] & cons;
         if (d0 == 0) continue;
-        const bool ok = qn_cone(A, C, S, T, W, col, i, d0, cnt);
-        if (!ok) {
-            if (lane == 0) C.header[0] = 1;
-            break;
-        }
-        u64 orT = 0;
-        for (int q = lane; q < cnt[T]; q += 64) orT |= S.diff(T, q);
-        for (int off = 32; off; off >>= 1) orT |= (u64)__shfl_xor((long long)orT, off);
-        const u64 acc = d0 & ~orT;                           // consensus survives the flip
-        if (acc) {
-            for (int l = 0; l <= T; ++l)
-                for (int q = lane; q < cnt[l]; q += 64) {    // the nodes of a list are distinct: one lane per word
-                    const u64 dq = S.diff(l, q) & acc;
-                    if (dq) C.L[l][(int64_t)S.node(l, q) * W + col] ^= dq;
-                }
-            mine += (long long)((acc >> lane) & 1);
-        }
-        __syncthreads();                                     // the commits land before the next candidate reads them
+        u64 acc;
+        if (!qn_try_commit(A, C, S, T, W, col, i, d0, cnt, acc)) break;
+        mine += (long long)((acc >> lane) & 1);
     }
     flipped[col * 64 + lane] = mine;
 }
@@ -357,7 +323,7 @@ __global__ void __launch_bounds__(64) k_quench(Adj A, QnCone C, int T, int64_t n
 //            pending candidate of lower rank within 2T: its node goes to the
 //            ready list and the slot takes the next candidate (an atomic
 //            cursor into the order) and walks its ball, once per candidate;
-//   commit   a wave per (ready node, word column) runs k_quench's body.
+//   commit   a wave per (ready node, word column) runs qn_try_commit, as k_quench does.
 // The pending candidate of lowest rank always wins its ball, so a round with
 // anything pending commits at least one candidate.
 struct QrState {
@@ -379,13 +345,12 @@ __device__ __forceinline__ unsigned long long qr_key(long long round, int32_t ra
 
 // The nodes within distance T of i, each once, into ball[0 .. cap): the cone's
 // candidate walk (a lane per frontier node, the lanes walking their rows
-// together) without the words.  Returns the count; ok = false when the ball
-// outgrew cap or a row names a node >= n (nothing is written out of bounds, the
-// ball is then incomplete).  One wave = the workgroup; wave-uniform control flow.
+// together) on one plain list that grows level by level.  Returns the count;
+// ok = false when the ball outgrew cap or a row names a node >= n (nothing is
+// written out of bounds, the ball is then incomplete).  Wave-uniform.
 template <class Adj>
 __device__ int qr_ball(const Adj& A, int T, int64_t n, uint32_t i, int32_t* ball, int cap, bool& ok) {
     const int lane = threadIdx.x;
-    const u64 below = (1ull << lane) - 1;
     if (lane == 0) ball[0] = (int32_t)i;
     __syncthreads();
     int nu = 1, f0 = 0;
@@ -395,36 +360,14 @@ __device__ int qr_ball(const Adj& A, int T, int64_t n, uint32_t i, int32_t* ball
             const bool have = base + lane < f1;
             const uint32_t v = have ? (uint32_t)ball[base + lane] : 0u;
             const int dg = have ? A.deg(v) : 0;
-            int longest = dg;
-            for (int off = 32; off; off >>= 1) {
-                const int o = __shfl_xor(longest, off);
-                longest = o > longest ? o : longest;
-            }
+            const int longest = qn_wave_max(dg);
             const int lanes = (f1 - base) < 64 ? (f1 - base) : 64;
             for (int e = 0; e < longest && ok; ++e) {
                 const bool valid = e < dg;
                 const uint32_t x = valid ? A.nbr(v, e) : kQnNoNode;
-                if (__ballot(valid && x >= (uint32_t)n)) { ok = false; break; }
-                u64 seen = 0;
-                for (int m = 0; m < lanes; ++m) {
-                    const uint32_t y = qn_lane32(x, m);
-                    if (__ballot(x == y) & ((1ull << m) - 1)) seen |= 1ull << m;
-                }
-                for (int b = 0; b < nu; b += 64) {
-                    const uint32_t have_c = (b + lane < nu) ? (uint32_t)ball[b + lane] : 0xfffffffeu;
-                    for (int m = 0; m < lanes; ++m) {
-                        const uint32_t y = qn_lane32(x, m);
-                        if (__ballot(have_c == y)) seen |= 1ull << m;
-                    }
-                }
-                const bool fresh = valid && !((seen >> lane) & 1);
-                const u64 mask = __ballot(fresh);
-                const int pos = nu + __popcll(mask & below);
-                const int total = nu + __popcll(mask);
-                if (total > cap) ok = false;
-                else if (fresh) ball[pos] = (int32_t)x;
-                nu = ok ? total : nu;
-                __syncthreads();
+                ok = !__ballot(valid && x >= (uint32_t)n) &&
+                     qn_offer(x, valid, lanes, nu, cap, [&](int q) { return (uint32_t)ball[q]; },
+                              [&](int q, uint32_t y) { ball[q] = (int32_t)y; });
             }
         }
         f0 = f1;
@@ -485,8 +428,8 @@ __global__ void __launch_bounds__(64) k_qr_check(Adj A, QrState Q, int T, int64_
     }
 }
 
-// k_quench's body for every (ready node, word column) pair.  The ready nodes
-// are further apart than 2T, so no pair reads a word another pair writes.
+// The try-and-commit of k_quench for every (ready node, word column) pair.  The
+// ready nodes are further apart than 2T, so no pair reads a word another writes.
 template <class Adj>
 __global__ void __launch_bounds__(64) k_qr_commit(Adj A, QnCone C, QrState Q, int T, int64_t n, int64_t W, int64_t R,
                                                   const u64* __restrict__ removable,
@@ -509,25 +452,9 @@ __global__ void __launch_bounds__(64) k_qr_commit(Adj A, QnCone C, QrState Q, in
         const u64 cons = C.header[1 + 64 * W + col] & qn_valid(col, W, R);
         const u64 d0 = C.L[0][(int64_t)i * W + col] & cons;
         if (d0 == 0) continue;
-        const bool ok = qn_cone(A, C, S, T, W, col, i, d0, cnt);
-        if (!ok) {
-            if (lane == 0) C.header[0] = 1;
-            __syncthreads();
-            continue;
-        }
-        u64 orT = 0;
-        for (int k = lane; k < cnt[T]; k += 64) orT |= S.diff(T, k);
-        for (int off = 32; off; off >>= 1) orT |= (u64)__shfl_xor((long long)orT, off);
-        const u64 acc = d0 & ~orT;
-        if (acc) {
-            for (int l = 0; l <= T; ++l)
-                for (int k = lane; k < cnt[l]; k += 64) {
-                    const u64 dq = S.diff(l, k) & acc;
-                    if (dq) C.L[l][(int64_t)S.node(l, k) * W + col] ^= dq;
-                }
-            if ((acc >> lane) & 1) atomicAdd(&flipped[col * 64 + lane], 1ull);
-        }
-        __syncthreads();                                     // the lists are reused by the next pair
+        u64 acc;                                             // an overflow is flagged; the other pairs go on
+        qn_try_commit(A, C, S, T, W, col, i, d0, cnt, acc);
+        if ((acc >> lane) & 1) atomicAdd(&flipped[col * 64 + lane], 1ull);
     }
 }
 
@@ -728,7 +655,7 @@ extern "C" int mjx_flip_gain_ell_rp(const int32_t* adj, int64_t n, int d, int64_
                                     const uint64_t* const* levels, const int64_t* caps, int lds_entries,
                                     void* scratch, int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus,
                                     int32_t* gain, void* stream) {
-    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (!adj_ell_ok(adj, d)) return MJX_EINVAL;
     return flip_gain_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, removable,
                          consensus, gain, stream);
 }
@@ -737,7 +664,7 @@ extern "C" int mjx_flip_gain_csr_rp(const int64_t* row_ptr, const int32_t* col, 
                                     const uint64_t* const* levels, const int64_t* caps, int lds_entries,
                                     void* scratch, int64_t scratch_bytes, uint64_t* removable, uint8_t* consensus,
                                     int32_t* gain, void* stream) {
-    if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
+    if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
     return flip_gain_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes,
                          removable, consensus, gain, stream);
 }
@@ -746,7 +673,7 @@ extern "C" int mjx_quench_ell_rp(const int32_t* adj, int64_t n, int d, int64_t R
                                  uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
                                  int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr,
                                  uint8_t* consensus, int64_t* flipped, void* stream) {
-    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (!adj_ell_ok(adj, d)) return MJX_EINVAL;
     return quench_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, cand, cand_ptr,
                       consensus, flipped, stream);
 }
@@ -755,7 +682,7 @@ extern "C" int mjx_quench_csr_rp(const int64_t* row_ptr, const int32_t* col, int
                                  uint64_t* const* levels, const int64_t* caps, int lds_entries, void* scratch,
                                  int64_t scratch_bytes, const int32_t* cand, const int64_t* cand_ptr,
                                  uint8_t* consensus, int64_t* flipped, void* stream) {
-    if (!row_ptr) return MJX_EINVAL;
+    if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
     return quench_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, cand,
                       cand_ptr, consensus, flipped, stream);
 }
@@ -773,7 +700,7 @@ extern "C" int mjx_quench_regions_ell_rp(const int32_t* adj, int64_t n, int d, i
                                          int64_t scratch_bytes, int64_t window, const uint64_t* removable,
                                          const int32_t* cand, int64_t ncand, uint8_t* consensus, int64_t* flipped,
                                          int64_t* stats, int64_t round0, int64_t rounds, void* stream) {
-    if (d < 0 || d > 255 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (!adj_ell_ok(adj, d)) return MJX_EINVAL;
     return quench_regions_run(AdjEll{adj, d}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes, window,
                               removable, cand, ncand, consensus, flipped, stats, round0, rounds, stream);
 }
@@ -783,7 +710,7 @@ extern "C" int mjx_quench_regions_csr_rp(const int64_t* row_ptr, const int32_t* 
                                          int64_t scratch_bytes, int64_t window, const uint64_t* removable,
                                          const int32_t* cand, int64_t ncand, uint8_t* consensus, int64_t* flipped,
                                          int64_t* stats, int64_t round0, int64_t rounds, void* stream) {
-    if (!row_ptr) return MJX_EINVAL;
+    if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
     return quench_regions_run(AdjCsr{row_ptr, col}, n, R, p, c, levels, caps, lds_entries, scratch, scratch_bytes,
                               window, removable, cand, ncand, consensus, flipped, stats, round0, rounds, stream);
 }

@@ -21,7 +21,7 @@
 // after a workgroup barrier.  Bits of one word may belong to several lanes:
 // they are turned with LDS atomics, whole words are stored by one lane.
 // Everything is integer.
-#include "mjx_common.h"
+#include "mjx_quench_parts.h"
 #include <algorithm>
 
 namespace mjx {
@@ -40,22 +40,6 @@ struct QjPlan {
     int64_t bytes;                // LDS of a job
 };
 
-struct QjEll {
-    const int32_t* adj;
-    int d;
-    __device__ __forceinline__ QjEll at(int64_t shift) const { return QjEll{adj ? adj + shift : adj, d}; }
-    __device__ __forceinline__ int deg(int) const { return d; }
-    __device__ __forceinline__ const int32_t* row(int v) const { return adj + (int64_t)v * d; }
-};
-
-struct QjCsr {
-    const int64_t* row_ptr;
-    const int32_t* col;
-    __device__ __forceinline__ QjCsr at(int64_t) const { return *this; }
-    __device__ __forceinline__ int deg(int v) const { return (int)(row_ptr[v + 1] - row_ptr[v]); }
-    __device__ __forceinline__ const int32_t* row(int v) const { return col + row_ptr[v]; }
-};
-
 __device__ __forceinline__ bool qj_bit(const uint32_t* L, int v) { return (L[v >> 5] >> (v & 31)) & 1u; }
 
 // sign(2 S + s_v) > 0 on level Lp: rows with multiplicity, degree 0 keeps the spin
@@ -70,14 +54,6 @@ __device__ __forceinline__ bool qj_new(const Adj& A, const uint32_t* Lp, int v, 
         if (k < (uint32_t)n) S += qj_bit(Lp, (int)k) ? 1 : -1;
     }
     return 2 * S + (qj_bit(Lp, v) ? 1 : -1) > 0;
-}
-
-__device__ __forceinline__ int qj_wave_max(int x) {
-    for (int off = 32; off; off >>= 1) {
-        const int o = __shfl_xor(x, off);
-        x = o > x ? o : x;
-    }
-    return x;
 }
 
 // Try the flip of node i (L_0[i] = +1, L_T all +1).  Wave-uniform; returns 1
@@ -112,7 +88,7 @@ __device__ int qj_try(const Adj& A, const QjPlan& P, uint32_t* lds, int n, int i
             const int v = have ? (int)prev[base + lane] : 0;
             const int dg = have ? A.deg(v) : -1;
             const int32_t* row = have ? A.row(v) : nullptr;
-            const int longest = qj_wave_max(dg);
+            const int longest = qn_wave_max(dg);
             for (int e = 0; e <= longest && !err; ++e) {
                 bool valid = e <= dg;
                 const uint32_t x = valid ? (e == 0 ? (uint32_t)v : (uint32_t)row[e - 1]) : 0u;
@@ -323,8 +299,8 @@ extern "C" int mjx_quench_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t
                                    int p, int c, const int64_t* caps, const uint64_t* s_np, const int32_t* order,
                                    int64_t order_stride_r, uint64_t* out_np, int64_t* flipped, int64_t* plus,
                                    uint8_t* consensus, int32_t* flag, void* stream) {
-    if (d < 0 || d > 255 || (d > 0 && !adj) || (graph_stride != 0 && graph_stride != n * d)) return MJX_EINVAL;
-    return quench_jobs_run(QjEll{adj, d}, n, graph_stride, R, K, p, c, caps, s_np, order, order_stride_r, out_np,
+    if (!adj_ell_ok(adj, d) || (graph_stride != 0 && graph_stride != n * d)) return MJX_EINVAL;
+    return quench_jobs_run(AdjEll{adj, d}, n, graph_stride, R, K, p, c, caps, s_np, order, order_stride_r, out_np,
                            flipped, plus, consensus, flag, stream);
 }
 
@@ -332,7 +308,7 @@ extern "C" int mjx_quench_jobs_csr(const int64_t* row_ptr, const int32_t* col, i
                                    int c, const int64_t* caps, const uint64_t* s_np, const int32_t* order,
                                    int64_t order_stride_r, uint64_t* out_np, int64_t* flipped, int64_t* plus,
                                    uint8_t* consensus, int32_t* flag, void* stream) {
-    if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
-    return quench_jobs_run(QjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
+    if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
+    return quench_jobs_run(AdjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
                            plus, consensus, flag, stream);
 }

@@ -68,6 +68,14 @@ def _host_n(graph, s, words):
     return int(np.shape(graph)[0])
 
 
+def _are_permutations(rows, n):
+    """rows: int64 (m, n) -> every row is a permutation of 0..n-1."""
+    if not rows.size:
+        return True
+    slots = rows + n * np.arange(rows.shape[0])[:, None]         # row j counts into its own n bins
+    return bool(rows.min() >= 0 and rows.max() < n and np.bincount(slots.ravel(), minlength=rows.size).max() == 1)
+
+
 def _check_order(order, seed, n):
     """``order`` as an int64 numpy permutation of 0..n-1, or None for the
     identity; host only."""
@@ -81,7 +89,7 @@ def _check_order(order, seed, n):
     if o.ndim != 1 or o.shape[0] != n or not np.issubdtype(o.dtype, np.integer):
         raise ValueError(f"order must be an integer permutation of 0..{n - 1}")
     o = o.astype(np.int64)
-    if o.size and (o.min() < 0 or o.max() >= n or np.bincount(o, minlength=n).max() != 1):
+    if not _are_permutations(o[None, :], n):
         raise ValueError(f"order must be a permutation of 0..{n - 1}")
     return o
 
@@ -97,24 +105,39 @@ def _check_symmetric(g):
                              "the light cone relies on it")
 
 
+def _spins_2d(s):
+    """+-1 spins (n,) or (R, n) -> (contiguous 2-D int8 / int32 / int64 device tensor, "s is a vector")."""
+    t = _device.to_device(s)
+    vector = t.dim() == 1
+    if vector:
+        t = t[None, :]
+    if t.dtype not in (torch.int8, torch.int32, torch.int64):
+        t = t.to(torch.int64)
+    return t.contiguous(), vector
+
+
+def _conf_like(conf, s, vector):
+    """conf: device spins (R, n) -> the shape, kind and dtype of the input ``s``."""
+    if vector:
+        conf = conf[0]
+    if isinstance(s, torch.Tensor):
+        return conf.to(device=s.device, dtype=s.dtype)
+    return conf.cpu().numpy().astype(np.asarray(s).dtype, copy=False)
+
+
 def _packed_input(g, s, words):
-    """-> (bits, R, W, ndim of the +-1 input or None for packed input)."""
+    """-> (bits, R, W, "the +-1 input is a vector" or None for packed input)."""
     if words is not None:
         bits = _device.to_device(s, torch.int64).reshape(-1)
         W = int(words)
         if W < 1 or bits.numel() != g.n * W:
             raise ValueError(f"packed spins hold {bits.numel()} words, n * words = {g.n * W}")
         return bits, 64 * W, W, None
-    t = _device.to_device(s)
-    ndim = t.dim()
-    if ndim == 1:
-        t = t[None, :]
+    t, vector = _spins_2d(s)
     if t.dim() != 2 or t.shape[1] != g.n:
         raise ValueError(f"spins must be (n,) or (R, n) with n = {g.n}")
-    if t.dtype not in (torch.int8, torch.int32, torch.int64):
-        t = t.to(torch.int64)
     R = t.shape[0]
-    return pack(t.contiguous()), R, _device.words_for(R), ndim
+    return pack(t), R, _device.words_for(R), vector
 
 
 def _levels(g, bits, W, T, copy):
@@ -152,20 +175,31 @@ def _check_overflow(scratch, what):
         raise _lib.MjxError(f"{what}: a light-cone list outgrew the ball bound of the graph")
 
 
+def _cone_call(entry, what, g, levels, R, p, c, T, caps, lds_entries, scratch_bytes):
+    """The set-up the level-based entry points share -> (call, consensus uint8 [R]).  ``call(*args)`` runs
+    mjx_<entry>_{ell,csr}_rp(graph, R, p, c, levels, caps, lds_entries, scratch, its bytes, *args, stream) on
+    one scratch area of ``scratch_bytes`` and raises when the overflow flag is up afterwards."""
+    dev = levels[0].device
+    scratch = _scratch(scratch_bytes, what, T, lds_entries, dev)
+    lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
+    kind, ga = _graph_args(g)
+
+    def call(*args):
+        _lib.call(f"mjx_{entry}_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch),
+                  scratch.numel() * 8, *args, _device.stream_handle())
+        _check_overflow(scratch, what)
+
+    return call, torch.empty(R, dtype=torch.uint8, device=dev)
+
+
 def _flip_gains_packed(g, levels, R, W, p, c, T, caps, lds_entries, gain):
     """Device call on cached levels -> (removable, consensus uint8 [R], gain int32 (n, 64 W) or None)."""
     dev = levels[0].device
-    lib = _lib.load()
-    scratch = _scratch(lib.mjx_flip_gain_scratch_bytes(g.n, R, T, caps, lds_entries), "flip_gains", T, lds_entries, dev)
-    lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
+    call, consensus = _cone_call("flip_gain", "flip_gains", g, levels, R, p, c, T, caps, lds_entries,
+                                 _lib.load().mjx_flip_gain_scratch_bytes(g.n, R, T, caps, lds_entries))
     removable = torch.empty(g.n * W, dtype=torch.int64, device=dev)
-    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
     gains = torch.empty((g.n, 64 * W), dtype=torch.int32, device=dev) if gain else None
-    kind, ga = _graph_args(g)
-    _lib.call(f"mjx_flip_gain_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch),
-              scratch.numel() * 8, _device.ptr(removable), _device.ptr(consensus), _device.ptr(gains),
-              _device.stream_handle())
-    _check_overflow(scratch, "flip_gains")
+    call(_device.ptr(removable), _device.ptr(consensus), _device.ptr(gains))
     return removable, consensus, gains
 
 
@@ -220,47 +254,39 @@ def _candidates(removable, n, W, order):
     return cand, cand_ptr
 
 
-def _quench_prepare(g, bits, R, W, p, c, T, order, lds_entries):
-    """The parallel part: copies of the levels, the initial removable mask and
-    the candidate lists -> (levels, caps, cand, cand_ptr)."""
+def _quench_prepare(g, bits, R, W, p, c, T, lds_entries):
+    """The parallel part of both schedules: the caps, copies of the levels and
+    the initial removable mask -> (levels, caps, removable)."""
     caps = _caps(g, T)
     levels = _levels(g, bits, W, T, copy=True)
     removable, _, _ = _flip_gains_packed(g, levels, R, W, p, c, T, caps, lds_entries, False)
-    cand, cand_ptr = _candidates(removable, g.n, W, order)
-    return levels, caps, cand, cand_ptr
+    return levels, caps, removable
 
 
 def _quench_pass(g, levels, R, W, p, c, T, caps, cand, cand_ptr, lds_entries):
     """The sequential part, one workgroup per word column; ``levels`` are
     updated in place -> (consensus uint8 [R], flipped int64 [R])."""
-    dev = levels[0].device
-    lib = _lib.load()
-    scratch = _scratch(lib.mjx_quench_scratch_bytes(R, T, caps, lds_entries), "quench", T, lds_entries, dev)
-    lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
-    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
-    flipped = torch.zeros(64 * W, dtype=torch.int64, device=dev)
-    kind, ga = _graph_args(g)
-    _lib.call(f"mjx_quench_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch), scratch.numel() * 8,
-              _device.ptr(cand) if cand.numel() else None, _device.ptr(cand_ptr), _device.ptr(consensus),
-              _device.ptr(flipped), _device.stream_handle())
-    _check_overflow(scratch, "quench")
+    call, consensus = _cone_call("quench", "quench", g, levels, R, p, c, T, caps, lds_entries,
+                                 _lib.load().mjx_quench_scratch_bytes(R, T, caps, lds_entries))
+    flipped = torch.zeros(64 * W, dtype=torch.int64, device=levels[0].device)
+    call(_device.ptr(cand) if cand.numel() else None, _device.ptr(cand_ptr), _device.ptr(consensus),
+         _device.ptr(flipped))
     return consensus, flipped[:R]
 
 
 def _quench_packed(g, bits, R, W, p, c, T, order, lds_entries, schedule="sequential", window=None):
     """-> (state = packed result (a new tensor), consensus uint8 [R], flipped int64 [R], candidates visited,
     the regions pass's {"rounds", "window", "max_commits"} or {})."""
+    levels, caps, removable = _quench_prepare(g, bits, R, W, p, c, T, lds_entries)
     if schedule == "regions":
-        caps = _caps(g, T)
-        levels = _levels(g, bits, W, T, copy=True)
-        removable, _, _ = _flip_gains_packed(g, levels, R, W, p, c, T, caps, lds_entries, False)
         cand, visited = _union_candidates(removable, g.n, W, order)
         consensus, flipped, info = _quench_regions_pass(g, levels, R, W, p, c, T, caps, removable, cand, window,
                                                         lds_entries)
-        return levels[0], consensus, flipped, visited, info
-    levels, caps, cand, cand_ptr = _quench_prepare(g, bits, R, W, p, c, T, order, lds_entries)
-    consensus, flipped = _quench_pass(g, levels, R, W, p, c, T, caps, cand, cand_ptr, lds_entries)
-    return levels[0], consensus, flipped, int(cand.numel()), {}
+    else:
+        cand, cand_ptr = _candidates(removable, g.n, W, order)
+        consensus, flipped = _quench_pass(g, levels, R, W, p, c, T, caps, cand, cand_ptr, lds_entries)
+        visited, info = int(cand.numel()), {}
+    return levels[0], consensus, flipped, visited, info
 
 
 SCHEDULES = ("sequential", "regions")
@@ -313,28 +339,21 @@ def _quench_regions_pass(g, levels, R, W, p, c, T, caps, removable, cand, window
     counter once per chunk of rounds and never enqueues more rounds than there
     are candidates."""
     dev = levels[0].device
-    lib = _lib.load()
     ncand = int(cand.numel())
     K = max(1, min(default_window(g.n, caps[T]) if window is None else window, ncand))
-    scratch = _scratch(lib.mjx_quench_regions_scratch_bytes(g.n, R, T, caps, lds_entries, K), "quench", T, lds_entries,
-                       dev)
-    lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
-    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
+    call, consensus = _cone_call("quench_regions", "quench", g, levels, R, p, c, T, caps, lds_entries,
+                                 _lib.load().mjx_quench_regions_scratch_bytes(g.n, R, T, caps, lds_entries, K))
     flipped = torch.empty(64 * W, dtype=torch.int64, device=dev)
     stats = torch.empty(4, dtype=torch.int64, device=dev)
-    kind, ga = _graph_args(g)
 
     def enqueue(round0, rounds):
-        _lib.call(f"mjx_quench_regions_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch),
-                  scratch.numel() * 8, K, _device.ptr(removable), _device.ptr(cand) if ncand else None, ncand,
-                  _device.ptr(consensus), _device.ptr(flipped), _device.ptr(stats), round0, rounds,
-                  _device.stream_handle())
+        call(K, _device.ptr(removable), _device.ptr(cand) if ncand else None, ncand, _device.ptr(consensus),
+             _device.ptr(flipped), _device.ptr(stats), round0, rounds)
         return [int(x) for x in stats.cpu().tolist()]
 
     launched = min(ncand, 16)
     left, rounds, most, _ = enqueue(0, launched)
     while left:
-        _check_overflow(scratch, "quench")
         if launched >= ncand:
             raise _lib.MjxError(f"quench: {left} of {ncand} candidates are left after {launched} rounds; every round "
                                 "with a pending candidate commits one")
@@ -342,7 +361,6 @@ def _quench_regions_pass(g, levels, R, W, p, c, T, caps, removable, cand, window
         chunk = min(ncand - launched, 1024, max(1, -(-left * rounds // max(1, ncand - left))))
         left, rounds, most, _ = enqueue(launched, chunk)
         launched += chunk
-    _check_overflow(scratch, "quench")
     return consensus, flipped[:R], {"rounds": rounds, "window": K, "max_commits": most}
 
 
@@ -380,7 +398,7 @@ def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, valid
         raise ValueError(f"order must be a permutation of 0..{g.n - 1}")
     if validate:
         _check_symmetric(g)
-    bits, R, W, ndim = _packed_input(g, s, words)
+    bits, R, W, vector = _packed_input(g, s, words)
     state, consensus, flipped, visited, info = _quench_packed(g, bits, R, W, p, c, T, order, lds_entries, schedule,
                                                               window)
     plus = popcount(state, g.n, words=W)[:R]
@@ -388,15 +406,8 @@ def quench(graph, s, p, c, order=None, seed=None, words=None, kernel=None, valid
     mag = torch.from_numpy((2 * plus.cpu().numpy() - g.n) / g.n)
     out = {"flipped": _like(flipped, s), "consensus": _like(consensus.to(torch.bool), s), "mag": _like(mag, s),
            "visited": visited, "state": state, "words": W, **info}
-    if words is not None:
-        return out
-    conf = unpack(state, g.n, R)
-    if ndim == 1:
-        conf = conf[0]
-    if isinstance(s, torch.Tensor):
-        out["conf"] = conf.to(device=s.device, dtype=s.dtype)
-    else:
-        out["conf"] = conf.cpu().numpy().astype(np.asarray(s).dtype, copy=False)
+    if words is None:
+        out["conf"] = _conf_like(unpack(state, g.n, R), s, vector)
     return out
 
 
@@ -436,15 +447,13 @@ def _check_orders(orders, seed, restarts, R, n):
         raise ValueError(f"restarts = {K} but orders holds {o.shape[1]} per start")
     if o.shape[0] not in (1, R):
         raise ValueError(f"orders of shape (R, K, n) need R = {R} starts, got {o.shape[0]}")
-    rows = o.reshape(-1, n)
-    if o.size and (o.min() < 0 or o.max() >= n or
-                   np.bincount((rows + n * np.arange(rows.shape[0])[:, None]).ravel(), minlength=rows.size).max() != 1):
+    if not _are_permutations(o.reshape(-1, n), n):
         raise ValueError(f"every row of orders must be a permutation of 0..{n - 1}")
     return np.ascontiguousarray(o, dtype=np.int32)
 
 
 def _host_shapes(graph, s):
-    """(graph per start?, n, R, ndim of s) without touching the device."""
+    """(graph per start?, n, R) without touching the device."""
     if isinstance(graph, Graph):
         stack, n = False, graph.n
     elif isinstance(graph, (list, tuple)) and any(isinstance(x, Graph) for x in graph):
@@ -463,7 +472,7 @@ def _host_shapes(graph, s):
         raise ValueError("no starts")
     if stack and int(gs[0]) != R:
         raise ValueError(f"a graph per start: {int(gs[0])} graphs for {R} starts")
-    return stack, n, R, len(ss)
+    return stack, n, R
 
 
 def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t):
@@ -518,7 +527,7 @@ def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all
     p, c, T = _steps(p, c)
     if kernel:
         raise ValueError(f"unknown kernel options {sorted(dict(kernel))}")
-    stack, n, R, ndim = _host_shapes(graph, s)
+    stack, n, R = _host_shapes(graph, s)
     K = int(restarts)
     orders = _check_orders(orders, seed, K, R, n)
     if stack:
@@ -543,12 +552,7 @@ def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all
     if lds < 0:
         raise ValueError(f"quench_restarts: a job of n = {n}, p + c - 1 = {T} (ball bound {list(caps)}) does not fit "
                          "the workgroup's LDS; quench is the path for this shape")
-    t = _device.to_device(s)
-    if t.dim() == 1:
-        t = t[None, :]
-    if t.dtype not in (torch.int8, torch.int32, torch.int64):
-        t = t.to(torch.int64)
-    t = t.contiguous()
+    t, vector = _spins_2d(s)
     dev, st, Wn = t.device, _device.stream_handle(), (n + 63) // 64
     s_np = torch.empty((R, Wn), dtype=torch.int64, device=dev)
     code, step = _device.dtype_code(t), n * t.element_size()
@@ -570,13 +574,7 @@ def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all
             _lib.call("mjx_unpack_np", bits.data_ptr() + j * Wn * 8, n, conf.data_ptr() + j * row, dc, st)
         return conf
 
-    conf_best = rows(state_best, t.dtype)
-    if ndim == 1:
-        conf_best = conf_best[0]
-    if isinstance(s, torch.Tensor):
-        conf_best = conf_best.to(device=s.device, dtype=s.dtype)
-    else:
-        conf_best = conf_best.cpu().numpy().astype(np.asarray(s).dtype, copy=False)
+    conf_best = _conf_like(rows(state_best, t.dtype), s, vector)
     out = {"mag": _like(torch.from_numpy(mag), s), "flipped": _like(flipped.view(R, K), s),
            "consensus": _like(consensus.to(torch.bool), s), "best": _like(torch.from_numpy(best), s),
            "conf_best": conf_best, "mag_best": _like(torch.from_numpy(mag_best), s), "state_best": state_best}

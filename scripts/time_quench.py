@@ -163,7 +163,8 @@ def main(argv=None):
     prep = {}
 
     def prepare():
-        prep["v"] = Q._quench_prepare(g, qbits, R, W, p, c, T, None, 0)
+        levels, caps_q, removable = Q._quench_prepare(g, qbits, R, W, p, c, T, 0)
+        prep["v"] = (levels, caps_q, *Q._candidates(removable, n, W, None))
 
     ms_prep, all_prep = median_ms(prepare, qreps)
     ms_pass, all_pass = median_ms(lambda: Q._quench_pass(g, prep["v"][0], R, W, p, c, T, *prep["v"][1:], 0), qreps,

@@ -10,7 +10,7 @@ with c = 1, the identity order.
   large   n = 1e6, R = 4096  (64 word columns),  median of 3 calls
 
 Per shape: ``quench(..., schedule="sequential")`` end to end (the path the
-package had before the regions pass: ``k_quench``, untouched), then for the
+package had before the regions pass: ``k_quench``), then for the
 default window and the ``--window-factors`` multiples of it the regions pass
 end to end and alone (``_quench_regions_pass`` on levels, mask and candidates
 prepared beforehand), with its rounds, window and commits per round.  Every
@@ -88,8 +88,7 @@ def run_shape(name, a):
     prep = {}
 
     def prepare():
-        levels = Q._levels(g, bits, W, T, copy=True)
-        removable, _, _ = Q._flip_gains_packed(g, levels, R, W, p, c, T, caps, 0, False)
+        levels, _, removable = Q._quench_prepare(g, bits, R, W, p, c, T, 0)
         prep["v"] = (levels, removable, Q._union_candidates(removable, n, W, None)[0])
 
     ms_prep, _ = median_ms(prepare, reps)

@@ -10,69 +10,27 @@ import numpy as np
 import pytest
 import torch
 
+import quench_cases
 import quench_oracle as qo
 from conftest import ROOT
+from quench_cases import _graph, hub_graph
 
 pytestmark = pytest.mark.gpu
 
 K_CASE = 3
-# name -> (graph kind, degree / mean degree, n, T, m_init, graph seed, start seed, starts R):
-# the constructors and seeds of the flip-gain / quench tests' table; R is the smallest
-# multiple of 16 at which the case is not degenerate (_not_degenerate)
-CASES = {
-    "rrg_d3_n200_T2": ("rrg", 3, 200, 2, 0.8, 2, 12, 32),
-    "rrg_d4_n96_T3": ("rrg", 4, 96, 3, 0.45, 3, 13, 16),
-    "rrg_d5_n120_T2": ("rrg", 5, 120, 2, 0.5, 4, 14, 16),
-    "rrg_d3_n130_T4": ("rrg", 3, 130, 4, 0.6, 5, 15, 16),
-    "er_n300_deg3_T2": ("er", 3.0, 300, 2, 0.9, 6, 16, 16),
-    "er_n300_deg5_T3": ("er", 5.0, 300, 3, 0.7, 7, 17, 32),
-    "rrg_d3_n64_T6": ("rrg", 3, 64, 6, 0.55, 8, 18, 16),
-}
-TABLE = [k for k in CASES if k != "rrg_d3_n64_T6"]
-
-
-def hub_graph(seed=9):
-    """ER graph of n = 300 (mean degree 3, isolated nodes kept) with node 0
-    joined to 80 further nodes, among them every isolated node but the last:
-    a row longer than a wave's 64 lanes, and one node of degree 0."""
-    import mjx
-    n, more = 300, 80
-    u, v = mjx.erdos_renyi_edges(n, 3.0 / (n - 1), seed=seed)
-    deg = np.bincount(np.concatenate([u, v]), minlength=n)
-    iso = np.flatnonzero(deg == 0)
-    iso = iso[iso != 0]
-    assert iso.size >= 1
-    lone = int(iso[-1])
-    nb0 = set(v[u == 0].tolist()) | set(u[v == 0].tolist()) | {0, lone}
-    others = [k for k in range(n) if k not in nb0 and k not in set(iso.tolist())]
-    extra = np.array(iso[:-1].tolist() + others[:more - (iso.size - 1)], dtype=np.int64)
-    assert extra.size == more
-    rp, col = mjx.csr_from_edges(n, np.concatenate([u, np.zeros(more, np.int64)]), np.concatenate([v, extra]))
-    d = np.diff(rp)
-    assert d[lone] == 0 and (d == 0).sum() == 1 and d[0] >= 70
-    return rp, col, lone
+# name -> starts R: the first R of the shared table's starts (``random_starts`` fills row by row, so they
+# are the starts of seed and R alone); R is the smallest multiple of 16 at which the case is not
+# degenerate (_not_degenerate).  "hub80": a row longer than a wave's 64 lanes, and one node of degree 0
+STARTS = {"rrg_d3_n200_T2": 32, "rrg_d4_n96_T3": 16, "rrg_d5_n120_T2": 16, "rrg_d3_n130_T4": 16,
+          "er_n300_deg3_T2": 16, "er_n300_deg5_T3": 32, "rrg_d3_n64_T6": 16, "hub80": 16}
+TABLE = [k for k in STARTS if k not in ("rrg_d3_n64_T6", "hub80")]
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
-    """-> (graph as the package takes it, oracle step, S (R, n), T).  Shared: never written."""
-    import mjx
-    if name == "hub":
-        rp, col, _ = hub_graph()
-        return ("csr", rp, col), qo.step_csr(rp, col), qo.random_starts(16, 300, 0.9, seed=19), 3
-    kind, d, n, T, m_init, gseed, sseed, R = CASES[name]
-    if kind == "rrg":
-        adj = mjx.random_regular_graph(d, n, seed=gseed)
-        return ("ell", adj), qo.step_ell(adj), qo.random_starts(R, n, m_init, sseed), T
-    rp, col, _ = mjx.erdos_renyi(n, d / (n - 1), seed=gseed, drop_isolated=True)
-    return ("csr", rp, col), qo.step_csr(rp, col), qo.random_starts(R, rp.shape[0] - 1, m_init, sseed), T
-
-
-@functools.lru_cache(maxsize=None)
-def _graph(name):
-    import mjx
-    spec = _case(name)[0]
-    return mjx.Graph.ell(spec[1]) if spec[0] == "ell" else mjx.Graph.csr(spec[1], spec[2])
+    """-> (graph as the package takes it, oracle step, S (STARTS[name], n), T).  Shared: never written."""
+    spec, step, S, T = quench_cases._case(name)
+    return spec, step, S[:STARTS[name]], T
 
 
 def _shared_orders(n, K=K_CASE):
@@ -294,9 +252,9 @@ def test_wrong_caps_raise_the_jobs_flag_and_a_shape_past_the_lds_is_refused(mjx_
 
 # ---- 6. hub and isolated node --------------------------------------------------------------
 def test_a_hub_past_64_lanes_and_an_isolated_node(mjx_mod):
-    _, step, S, T = _case("hub")
-    rp, col, lone = hub_graph()
-    g = _graph("hub")
+    _, step, S, T = _case("hub80")
+    rp, col, lone = hub_graph(more=80)
+    g = _graph("hub80")
     assert np.diff(rp)[0] >= 70
     caps = mjx_mod.SAReplicasER.ball_bound(g, T)
     assert caps[T] > 64, "the lists must be longer than one wave"
