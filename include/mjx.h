@@ -591,7 +591,7 @@ int mjx_hpr_q_ii(int dtype, const void* chi, int64_t E, int p, int c, void* ii, 
  * column and bias layouts as mjx_hpr_update.  Jacobi: every class reads chi_in
  * and writes its rows of chi_out.  w_plus/w_minus = exp(-lmbd*x_a[0]/n);
  * 2 <= p+c <= 4, any D <= 255.  A class whose count table (2^(T-1)*(D+1)^T
- * elements per message) does not fit the 160 KiB LDS keeps it in `scratch`:
+ * elements per message, double for either dtype) does not fit the 160 KiB LDS keeps it in `scratch`:
  * mjx_hpr_er_scratch_bytes(dtype, D, p, c) per message in flight (0: LDS
  * suffices, -1: unsupported); the call then runs ceil(m / (scratch_bytes /
  * that)) launches (MJX_ERANGE if scratch holds not even one table). */

@@ -20,6 +20,14 @@
 // over ALL x_k (HPR sums every sender trajectory; BDCM only attractor-ending
 // ones), then directional cumulative sums, so every output is one lookup
 // (the same rearrangement as mjx_bdcm.hip and mjx_hpr_impl.h).
+//
+// The table and the incoming messages are held in double for float messages
+// too (Acc): a row is a sum of products of D messages, and with reinforced,
+// saturating messages (weights exp(-+lmbd/n), lmbd = 25 n by default) every
+// entry of a row shrinks by a decade per iteration; in float the products
+// fell into the denormals, the normalisation by the row sum blew the lost
+// digits up, and the float loop left the float64 one within 40 iterations.
+// Only the loads of chi / biases and the store of the new row are float.
 #include "mjx_common.h"
 #include <math.h>
 
@@ -28,6 +36,7 @@ namespace hprer {
 
 constexpr int kMaxT = 4;
 constexpr size_t kMaxLds = 160 * 1024;
+using Acc = double;                   // type of the count table and of M, for either message type
 
 struct Geo {
     int T, P, D, X, XV, B, S, ab;     // ab: index bit 0 (x_a[T-1]) of the attractor spin
@@ -62,9 +71,9 @@ static bool make_geo(int D, int p, int c, int attr_value, Geo* g) {
 }
 
 template <typename S_>
-static size_t tab_bytes(const Geo& g) { return (size_t)g.XV * g.S * sizeof(S_); }
+static size_t tab_bytes(const Geo& g) { return (size_t)g.XV * g.S * sizeof(Acc); }
 template <typename S_>
-static size_t m_bytes(const Geo& g) { return (size_t)g.D * g.XV * g.X * sizeof(S_); }
+static size_t m_bytes(const Geo& g) { return (size_t)g.D * g.XV * g.X * sizeof(Acc); }
 template <typename S_>
 static size_t lds_bytes(const Geo& g) { return tab_bytes<S_>(g) + m_bytes<S_>(g); }
 
@@ -120,11 +129,11 @@ template <typename S_>
 __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, S_* __restrict__ chi_out,
                                                     const S_* __restrict__ biases, const int32_t* __restrict__ rows,
                                                     const int32_t* __restrict__ inc,
-                                                    const int32_t* __restrict__ inc_src, Geo g, S_ w_plus,
-                                                    S_ w_minus, S_ damp, int64_t e0, S_* __restrict__ gtab) {
+                                                    const int32_t* __restrict__ inc_src, Geo g, Acc w_plus,
+                                                    Acc w_minus, Acc damp, int64_t e0, Acc* __restrict__ gtab) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    S_* M = reinterpret_cast<S_*>(smem_raw);
-    S_* tab = gtab ? gtab + (size_t)blockIdx.x * g.XV * g.S : M + (size_t)g.D * g.XV * g.X;
+    Acc* M = reinterpret_cast<Acc*>(smem_raw);
+    Acc* tab = gtab ? gtab + (size_t)blockIdx.x * g.XV * g.S : M + (size_t)g.D * g.XV * g.X;
     const int lane = threadIdx.x;
     const int64_t e = e0 + blockIdx.x;
     const int X = g.X, NC = X * X, XV = g.XV, S = g.S, D = g.D, ab = g.ab, T = g.T;
@@ -133,13 +142,13 @@ __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, 
         const int m = q / (XV * X), r = q % (XV * X), a = r / X, k = r % X;
         const int64_t row = inc[e * D + m];
         const int64_t src = inc_src[e * D + m];
-        const S_ b = biases[2 * src + (hspin(k, 0, T) > 0 ? 0 : 1)];
-        M[q] = b * chi[row * NC + k * X + (2 * a + ab)];
+        const Acc b = biases[2 * src + (hspin(k, 0, T) > 0 ? 0 : 1)];
+        M[q] = b * (Acc)chi[row * NC + k * X + (2 * a + ab)];
     }
-    for (int q = lane; q < XV * S; q += 64) tab[q] = S_(0);
+    for (int q = lane; q < XV * S; q += 64) tab[q] = Acc(0);
     __syncthreads();
     if (D == 0) {
-        if (lane < XV) tab[lane * S] = S_(1);
+        if (lane < XV) tab[lane * S] = Acc(1);
     } else {
         for (int q = lane; q < XV * X; q += 64) {
             const int a = q / X, k = q % X;
@@ -149,11 +158,11 @@ __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, 
     __syncthreads();
     const int tot = XV * S;
     for (int m = 1; m < D; ++m) {
-        const S_* Mm = M + m * XV * X;
+        const Acc* Mm = M + m * XV * X;
         // in place, top-down: an entry only reads entries at or below itself
         for (int base = ((tot - 1) / 64) * 64; base >= 0; base -= 64) {
             const int q = base + lane;
-            S_ acc = S_(0);
+            Acc acc = Acc(0);
             if (q < tot) {
                 const int a = q / S, i = q % S;
                 int dg[kMaxT];
@@ -184,8 +193,8 @@ __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, 
         const int step = g.pw[t], span = step * g.B;
         for (int L = lane; L < lines; L += 64) {
             const int a = L / (S / g.B), r = L % (S / g.B);
-            S_* p = tab + a * S + (r / step) * span + (r % step);
-            S_ run = S_(0);
+            Acc* p = tab + a * S + (r / step) * span + (r % step);
+            Acc run = Acc(0);
             if (cond_dir(g, 2 * a + ab, t) > 0) {
                 for (int j = D; j >= 0; --j) {
                     run += p[j * step];
@@ -202,12 +211,12 @@ __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, 
     }
     // outputs: every column of the row (x_a[T-1] != attr: chi_new = 0)
     constexpr int CPL = 1024 / 64;                     // NC <= 256 at T <= 4: at most 4 per lane
-    S_ v[CPL / 4];
-    S_ rs = S_(0);
+    Acc v[CPL / 4];
+    Acc rs = Acc(0);
 #pragma unroll
     for (int j = 0; j < CPL / 4; ++j) {
         const int col = lane + 64 * j;
-        S_ x = S_(0);
+        Acc x = Acc(0);
         if (col < NC) {
             const int xa = col / X, xb = col % X;
             if ((xa & 1) == ab) {
@@ -220,11 +229,12 @@ __global__ void __launch_bounds__(64) k_hpr_er_edge(const S_* __restrict__ chi, 
     }
     rs = wave_sum(rs);
     const int64_t row = rows[e];
-    const S_ inv = S_(1) / rs;
+    const Acc inv = Acc(1) / rs;
 #pragma unroll
     for (int j = 0; j < CPL / 4; ++j) {
         const int col = lane + 64 * j;
-        if (col < NC) chi_out[row * NC + col] = damp * (v[j] * inv) + (S_(1) - damp) * chi[row * NC + col];
+        if (col < NC)
+            chi_out[row * NC + col] = (S_)(damp * (v[j] * inv) + (Acc(1) - damp) * (Acc)chi[row * NC + col]);
     }
 }
 
@@ -265,7 +275,7 @@ static int update_impl(const void* chi_in, void* chi_out, const void* biases, co
         const int64_t cnt = (m - e0 < per) ? m - e0 : per;
         if (cnt > (int64_t)INT32_MAX) return MJX_ERANGE;
         kern<<<(unsigned)cnt, 64, lds, st>>>((const S_*)chi_in, (S_*)chi_out, (const S_*)biases, rows, inc, inc_src, g,
-                                             (S_)w_plus, (S_)w_minus, (S_)damp, e0, in_lds ? nullptr : (S_*)scratch);
+                                             w_plus, w_minus, damp, e0, in_lds ? nullptr : (Acc*)scratch);
         MJX_LAUNCH_CHECK("k_hpr_er_edge");
     }
     return MJX_OK;

@@ -101,7 +101,6 @@ def _chi_new(chi, biases, inr, src, n, d, p, c, attr_value, lmbd_in):
     bs = np.where(plus0[None, :], biases[src][:, 0:1], biases[src][:, 1:2])     # (2E, X)
     M = M * bs[inr][..., None]
     nb = d ** T
-    digits = np.array(list(itertools.product(range(d), repeat=T)), dtype=np.int64)
     pw = d ** np.arange(T - 1, -1, -1)
     x01 = (tr == 1).astype(np.int64)                           # +1 -> 1
     LL = np.zeros((R, X, nb), dtype=np.float64)
@@ -110,14 +109,15 @@ def _chi_new(chi, biases, inr, src, n, d, p, c, attr_value, lmbd_in):
     else:
         for ik in range(X):
             LL[:, :, int(x01[ik] @ pw)] += M[:, 0, ik, :]
+    box = (R, X) + (d,) * T
     for m in range(1, d - 1):
         L = np.zeros_like(LL)
         for ik in range(X):
-            off = int(x01[ik] @ pw)
-            # only source states whose digits stay < d after the shift
-            valid = np.all(digits + x01[ik] < d, axis=1)
-            srcs = np.nonzero(valid)[0]
-            L[:, :, srcs + off] += LL[:, :, srcs] * M[:, m, ik, :][:, :, None]
+            # only source states whose digits stay < d after the shift: as slices of the (d,)*T
+            # box (the same sums in the same order as indexing the flat table, much faster)
+            to = (slice(None),) * 2 + tuple(slice(1, None) if x else slice(None) for x in x01[ik])
+            frm = (slice(None),) * 2 + tuple(slice(None, -1) if x else slice(None) for x in x01[ik])
+            L.reshape(box)[to] += LL.reshape(box)[frm] * M[:, m, ik, :].reshape((R, X) + (1,) * T)
         LL = L
     A = A_factor(T, p, c, d, attr_value)
     w = np.exp(-lmbd_in * tr[:, 0] / n)                        # exp(-lmbd*xi[0]/n)
