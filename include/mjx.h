@@ -98,11 +98,31 @@ int mjx_rollout_ell_rp_multi(const int32_t* adj, int64_t n, int d, int64_t R, co
 /* The replica-packed rollout run slice by slice: slice q of S covers word units
  * [q*U/S, (q+1)*U/S) of every node (U = words/2 16-byte units, or words if
  * odd); replicas never interact, so the result is identical for every S.
- * slices = 0 picks S from the state size (mjx_rollout_ell_rp uses that).
+ * slices = 0 follows mjx_rollout_ell_rp_plan (mjx_rollout_ell_rp uses that).
  * S must divide U (MJX_EINVAL otherwise). */
 int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, int64_t words,
                               const uint64_t* s_in, uint64_t* s_out, uint64_t* tmp,
                               int steps, int slices, unsigned long long* counts, void* stream);
+/* The same rollout over a slice-major intermediate state: the states between
+ * the sweeps are kept as [S][n][words/S] (slice q's rows one contiguous region),
+ * so a sliced sweep gathers from a region small enough to stay in the last-level
+ * cache; s_in and s_out keep the node-major layout and tmp stays pure scratch.
+ * slices >= 1 must divide U.  first_sliced == 0: the first sweep is one launch
+ * over whole rows that writes every region, later sweeps run slice by slice
+ * (s_out serves as second scratch buffer when steps >= 3); first_sliced != 0:
+ * every sweep runs slice by slice, a slice's whole chain before the next slice
+ * starts, through two regions of tmp.  steps <= 1 or slices == 1 run as
+ * mjx_rollout_ell_rp_sliced.  The result is identical for every choice. */
+int mjx_rollout_ell_rp_sm(const int32_t* adj, int64_t n, int d, int64_t words,
+                          const uint64_t* s_in, uint64_t* s_out, uint64_t* tmp,
+                          int steps, int slices, int first_sliced,
+                          unsigned long long* counts, void* stream);
+/* What slices = 0 runs (host only, no device call): *slices, *slice_major
+ * (0: mjx_rollout_ell_rp_sliced's node-major slicing, 1: mjx_rollout_ell_rp_sm)
+ * and *first_sliced.  One node-major slice when the state fits the cache, when
+ * steps < 2, or when no slice count dividing U fits the cache budget. */
+int mjx_rollout_ell_rp_plan(int64_t n, int d, int64_t words, int steps,
+                            int* slices, int* slice_major, int* first_sliced);
 int mjx_rollout_csr_np(const int64_t* row_ptr, const int32_t* col, int64_t n,
                        const uint64_t* s_in, uint64_t* s_out, uint64_t* tmp,
                        int steps, unsigned long long* counts, void* stream);

@@ -503,18 +503,62 @@ __device__ __forceinline__ void count_epilogue(VertCounter<VW, NK>& vc, bool act
     }
 }
 
+// Row views of a launch's state arrays.  The input and the output of a sweep
+// each have their own:
+//   kNodeRows   the caller's layout: node v's unit u at base + v*W + u*VW;
+//   kSliceRows  slice-major [S][n][ws]: the launch's units are cut into runs of
+//               `us` (ws = us*VW words); run q of node v lies at
+//               base + (q*n + v)*ws, a run being one contiguous region of n rows
+//               (a launch over one slice has one run: base points at its region).
+// A thread's unit is fixed, so a slice view is a word offset computed once
+// (slice_off) and a row stride.  The geometry of the slice views rides behind
+// the other kernel arguments; a node-to-node instantiation never reads it and
+// addresses its rows as base + v*W + unit*VW.
+enum RowKind { kNodeRows = 0, kSliceRows = 1 };
+struct SliceGeom { int64_t in_ws, in_us, out_ws, out_us; };
+// the kernel argument: empty when both views are node-major
+template <bool SLICED> struct GeomArg {
+    SliceGeom g;
+    __host__ __device__ GeomArg(const SliceGeom& x) : g(x) {}
+    __device__ __forceinline__ const SliceGeom& get() const { return g; }
+};
+template <> struct GeomArg<false> {
+    __host__ __device__ GeomArg(const SliceGeom&) {}
+    __device__ __forceinline__ SliceGeom get() const { return SliceGeom{0, 1, 0, 1}; }
+};
+
+// word offset of the thread's unit in row 0 of its run (slice views only)
+template <int KIND, int VW>
+__device__ __forceinline__ int64_t slice_off(int64_t n, int64_t unit, int64_t unit0, int64_t ws, int64_t us) {
+    if constexpr (KIND == kNodeRows) {
+        return 0;
+    } else {
+        const int u = (int)(unit - unit0), q = u / (int)us;
+        return (int64_t)q * n * ws + (int64_t)(u - q * (int)us) * VW;
+    }
+}
+// node v's unit in the array at p
+template <int KIND, int VW, typename T>
+__device__ __forceinline__ T* row_at(T* __restrict__ p, int64_t v, int64_t W, int64_t unit, int64_t ws, int64_t soff) {
+    if constexpr (KIND == kNodeRows) return p + v * W + unit * VW;
+    else return p + v * ws + soff;
+}
+
 // BS: block size (a 1024-thread counting sweep, 4x fewer global count atomics,
 // measured slower on MI355X: 537 vs 508 us at the bench size -- kept at 256).
-template <int D, int VW, bool COUNT, int BS = kBlock>
+template <int D, int VW, bool COUNT, int BS = kBlock, int IK = kNodeRows, int OK = kNodeRows>
 __global__ void __launch_bounds__(BS) k_sweep_ell_rp(const int32_t* __restrict__ adj, int64_t n, int64_t W,
                                                      const u64* __restrict__ s_in, u64* __restrict__ s_out,
                                                      unsigned long long* __restrict__ counts, int use_lds,
-                                                     int64_t unit0, int64_t Us) {
+                                                     int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga) {
     extern __shared__ unsigned lds_cnt[];
+    const SliceGeom sg = ga.get();
     const int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x;
     const int64_t slots = ((int64_t)gridDim.x * BS) / Us;
     const int64_t unit = unit0 + t % Us, slot = t / Us;
     const bool active = slot < slots;
+    const int64_t ioff = slice_off<IK, VW>(n, unit, unit0, sg.in_ws, sg.in_us);
+    const int64_t ooff = slice_off<OK, VW>(n, unit, unit0, sg.out_ws, sg.out_us);
     VertCounter<VW> vc;
     if constexpr (COUNT) {
         vc.reset();
@@ -526,8 +570,8 @@ __global__ void __launch_bounds__(BS) k_sweep_ell_rp(const int32_t* __restrict__
             load_adj<D>(adj, v, k);
             u64 x[D][VW], own[VW], out[VW];
 #pragma unroll
-            for (int j = 0; j < D; ++j) ldv<VW>(s_in + (int64_t)k[j] * W + unit * VW, x[j]);
-            ldv<VW>(s_in + v * W + unit * VW, own);
+            for (int j = 0; j < D; ++j) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[j], W, unit, sg.in_ws, ioff), x[j]);
+            ldv<VW>(row_at<IK, VW>(s_in, v, W, unit, sg.in_ws, ioff), own);
 #pragma unroll
             for (int q = 0; q < VW; ++q) {
                 u64 xs[D];
@@ -535,7 +579,7 @@ __global__ void __launch_bounds__(BS) k_sweep_ell_rp(const int32_t* __restrict__
                 for (int j = 0; j < D; ++j) xs[j] = x[j][q];
                 out[q] = majority_fixed<D>(xs, own[q]);
             }
-            stv<VW>(s_out + v * W + unit * VW, out);
+            stv<VW>(row_at<OK, VW>(s_out, v, W, unit, sg.out_ws, ooff), out);
             if constexpr (COUNT) {
                 vc.add(out);
                 if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
@@ -546,14 +590,15 @@ __global__ void __launch_bounds__(BS) k_sweep_ell_rp(const int32_t* __restrict__
 }
 
 // runtime degree (ELL rows of length d) and CSR rows; KB counter planes
-template <int VW, bool COUNT, bool CSR>
+template <int VW, bool COUNT, bool CSR, int IK = kNodeRows, int OK = kNodeRows>
 __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restrict__ adj, int d,
                                                          const int64_t* __restrict__ row_ptr,
                                                          const int32_t* __restrict__ col,
                                                          const int32_t* __restrict__ order, int64_t n, int64_t W,
                                                          const u64* __restrict__ s_in, u64* __restrict__ s_out,
                                                          unsigned long long* __restrict__ counts, int use_lds,
-                                                         int64_t unit0, int64_t Us) {
+                                                         int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga) {
+    const SliceGeom sg = ga.get();
     // order (nullable): node visiting order; sorted by degree it keeps the two
     // nodes a wave holds at one trip count (irregular ER rows)
     extern __shared__ unsigned lds_cnt[];
@@ -561,6 +606,8 @@ __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restri
     const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
     const int64_t unit = unit0 + t % Us, slot = t / Us;
     const bool active = slot < slots;
+    const int64_t ioff = slice_off<IK, VW>(n, unit, unit0, sg.in_ws, sg.in_us);
+    const int64_t ooff = slice_off<OK, VW>(n, unit, unit0, sg.out_ws, sg.out_us);
     VertCounter<VW, 10> vc;     // up to 1023 nodes per thread between flushes (N = 1e7 rows)
     if constexpr (COUNT) {
         vc.reset();
@@ -588,7 +635,7 @@ __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restri
                 for (int m = 0; m < 4; ++m) k[m] = nbr[j + m];
                 u64 x[4][VW];
 #pragma unroll
-                for (int m = 0; m < 4; ++m) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
+                for (int m = 0; m < 4; ++m) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[m], W, unit, sg.in_ws, ioff), x[m]);
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -602,7 +649,7 @@ __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restri
                 u64 x[3][VW];
 #pragma unroll
                 for (int m = 0; m < 3; ++m)
-                    if (m < rest) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
+                    if (m < rest) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[m], W, unit, sg.in_ws, ioff), x[m]);
 #pragma unroll
                 for (int m = 0; m < 3; ++m)
                     if (m < rest)
@@ -610,10 +657,10 @@ __global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restri
                         for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
             }
             u64 own[VW], out[VW];
-            ldv<VW>(s_in + v * W + unit * VW, own);
+            ldv<VW>(row_at<IK, VW>(s_in, v, W, unit, sg.in_ws, ioff), own);
 #pragma unroll
             for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(deg, own[q]);
-            stv<VW>(s_out + v * W + unit * VW, out);
+            stv<VW>(row_at<OK, VW>(s_out, v, W, unit, sg.out_ws, ooff), out);
             if constexpr (COUNT) {
                 vc.add(out);
                 if (vc.added == (1 << decltype(vc)::KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
@@ -1343,24 +1390,25 @@ static int launch_sweep_csr_np(const int64_t* rp, const int32_t* col, int64_t n,
 
 constexpr int kCountBlock = kBlock;
 
-template <int VW, bool COUNT>
+template <int VW, bool COUNT, int IK = kNodeRows, int OK = kNodeRows>
 static void launch_ell_rp_vw(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
                              unsigned long long* counts, int grid, size_t lds, int use_lds, int64_t unit0,
-                             int64_t Us, hipStream_t st) {
+                             int64_t Us, const SliceGeom& sg, hipStream_t st) {
     constexpr int BS = COUNT ? kCountBlock : kBlock;
     (void)grid;
     auto ell = [&](auto kern) {
         const int g = resident_grid(kern, BS, lds, n * Us);
-        kern<<<g, BS, lds, st>>>(adj, n, W, in, out, counts, use_lds, unit0, Us);
+        kern<<<g, BS, lds, st>>>(adj, n, W, in, out, counts, use_lds, unit0, Us, GeomArg<(IK | OK) != 0>(sg));
     };
     switch (d) {
-        case 3: ell(k_sweep_ell_rp<3, VW, COUNT, BS>); break;
-        case 4: ell(k_sweep_ell_rp<4, VW, COUNT, BS>); break;
-        case 6: ell(k_sweep_ell_rp<6, VW, COUNT, BS>); break;
+        case 3: ell(k_sweep_ell_rp<3, VW, COUNT, BS, IK, OK>); break;
+        case 4: ell(k_sweep_ell_rp<4, VW, COUNT, BS, IK, OK>); break;
+        case 6: ell(k_sweep_ell_rp<6, VW, COUNT, BS, IK, OK>); break;
         default: {
-            auto kern = k_sweep_gen_rp<VW, COUNT, false>;
+            auto kern = k_sweep_gen_rp<VW, COUNT, false, IK, OK>;
             const int g = resident_grid(kern, kBlock, lds, n * Us);
-            kern<<<g, kBlock, lds, st>>>(adj, d, nullptr, nullptr, nullptr, n, W, in, out, counts, use_lds, unit0, Us);
+            kern<<<g, kBlock, lds, st>>>(adj, d, nullptr, nullptr, nullptr, n, W, in, out, counts, use_lds, unit0, Us,
+                                         GeomArg<(IK | OK) != 0>(sg));
             break;
         }
     }
@@ -1379,31 +1427,48 @@ static int rp_geometry(int64_t n, int64_t W, int64_t Us, int* grid, int* vw, int
 
 // Replica slices of a replica-packed rollout: slice q covers units
 // [q*U/S, (q+1)*U/S).  Replicas never interact, so a rollout can run slice by
-// slice; a slice's state (n * W/S words) is small enough to stay in the 256 MB
-// Infinity Cache between the sweeps that re-read it.
+// slice (what that is worth: the plan below, mjx_rollout_ell_rp_plan).
 static int64_t units_of(int64_t W) { return (W % 2 == 0) ? W / 2 : W; }
 
-// Measured on MI355X (tools/slice_sweep.py, profiles/r01_slice_sweep.log): at
-// N=1e6, R=4096 one slice (512-B rows) runs at 6.2 TB/s, 2 slices at 6.1, 4 at
-// 4.9, 8 at 2.8 -- shorter contiguous gathers cost more than the Infinity Cache
-// returns -- so the automatic choice is a single slice.
-static int auto_slices(int64_t, int64_t) { return 1; }
-
-static int launch_sweep_ell_rp(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
-                               unsigned long long* counts, int64_t unit0, int64_t Us, hipStream_t st) {
+// One sweep over the units [unit0, unit0 + Us) of every node, `in` read through
+// a view of kind ik and `out` written through one of kind ok (RowKind; sg holds
+// the slice-major geometry, unused by node-major views).  The count rides only
+// on a sweep whose output is node-major (the last of a rollout).
+static int launch_sweep_ell_rp_v(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, int ik, u64* out,
+                                 int ok, const SliceGeom& sg, unsigned long long* counts, int64_t unit0,
+                                 int64_t Us, hipStream_t st) {
     int grid, vw, use_lds; size_t lds;
     int rc = rp_geometry(n, W, Us, &grid, &vw, &use_lds, &lds);
     if (rc) return rc;
     if (!counts) { lds = 0; use_lds = 0; }
-    if (vw == 2) {
-        if (counts) launch_ell_rp_vw<2, true>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, st);
-        else launch_ell_rp_vw<2, false>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, st);
-    } else {
-        if (counts) launch_ell_rp_vw<1, true>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, st);
-        else launch_ell_rp_vw<1, false>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, st);
-    }
+    if (counts && ok != kNodeRows) return MJX_EINVAL;
+#define MJX_ELL(VWV, C, IKV, OKV) \
+    launch_ell_rp_vw<VWV, C, IKV, OKV>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, sg, st)
+#define MJX_ELL_VIEWS(VWV)                                                           \
+    do {                                                                             \
+        if (ik == kNodeRows && ok == kNodeRows) {                                    \
+            if (counts) MJX_ELL(VWV, true, kNodeRows, kNodeRows);                    \
+            else MJX_ELL(VWV, false, kNodeRows, kNodeRows);                          \
+        } else if (ik == kNodeRows) {                                                \
+            MJX_ELL(VWV, false, kNodeRows, kSliceRows);                              \
+        } else if (ok == kSliceRows) {                                               \
+            MJX_ELL(VWV, false, kSliceRows, kSliceRows);                             \
+        } else {                                                                     \
+            if (counts) MJX_ELL(VWV, true, kSliceRows, kNodeRows);                   \
+            else MJX_ELL(VWV, false, kSliceRows, kNodeRows);                         \
+        }                                                                            \
+    } while (0)
+    if (vw == 2) MJX_ELL_VIEWS(2); else MJX_ELL_VIEWS(1);
+#undef MJX_ELL_VIEWS
+#undef MJX_ELL
     MJX_LAUNCH_CHECK("sweep_ell_rp");
     return MJX_OK;
+}
+
+static int launch_sweep_ell_rp(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
+                               unsigned long long* counts, int64_t unit0, int64_t Us, hipStream_t st) {
+    return launch_sweep_ell_rp_v(adj, n, d, W, in, kNodeRows, out, kNodeRows, SliceGeom{0, 1, 0, 1}, counts, unit0, Us,
+                                 st);
 }
 
 static int launch_sweep_csr_rp(const int64_t* rp, const int32_t* col, const int32_t* order, int64_t n, int64_t W,
@@ -1417,7 +1482,8 @@ static int launch_sweep_csr_rp(const int64_t* rp, const int32_t* col, const int3
     do {                                                                                                     \
         auto kern = k_sweep_gen_rp<VWV, C, true>;                                                            \
         grid = resident_grid(kern, kBlock, lds, n * Us);                                                     \
-        kern<<<grid, kBlock, lds, st>>>(nullptr, 0, rp, col, order, n, W, in, out, counts, use_lds, unit0, Us); \
+        kern<<<grid, kBlock, lds, st>>>(nullptr, 0, rp, col, order, n, W, in, out, counts, use_lds, unit0, Us, \
+                                        GeomArg<false>(SliceGeom{0, 1, 0, 1}));                              \
     } while (0)
     if (vw == 2) {
         if (counts) MJX_CSR(2, true); else MJX_CSR(2, false);
@@ -1500,30 +1566,141 @@ extern "C" int mjx_sweep_ell_np_range(const int32_t* adj, int64_t n, int d, int6
     return launch_sweep_ell_np(adj, row_lo, row_hi, d, (const u64*)s_in, (u64*)s_out, counts, as_stream(stream));
 }
 
-extern "C" int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
-                                         uint64_t* s_out, uint64_t* tmp, int steps, int slices,
-                                         unsigned long long* counts, void* stream) {
+// ---- automatic plan of the replica-packed ELL rollout ---------------------
+// Host only.  Measured on MI355X at N=1e6, R=4096, d=4 (tools/slice_major_ab.py,
+// profiles/slice_major_ab.log): gathers of short rows are
+// slow wherever the rows come from -- 512- and 256-byte rows run at 6.5 TB/s,
+// 128-byte rows at 5.9, 64-byte rows at 3.5-4.4, contiguous slice-major regions
+// that fit the Infinity Cache included -- so slicing the state down to the
+// cache loses.  What does pay, a little, is running a slice's sweeps back to
+// back (the sliced first sweep of mjx_rollout_ell_rp_sm) with rows of at least
+// 256 bytes: part of what one sweep wrote is still in the cache when the next
+// reads it (2 slices: 0.936 ms against 0.950 for a 2-sweep step, 1.381 against
+// 1.426 for 3 sweeps).  kMinSliceRow is the shortest row taken; kSliceBudget
+// bounds what one sliced sweep touches (its input region, the lines it writes,
+// the adjacency) to twice the cache, the only size measured.
+constexpr int64_t kCacheBytes = 256ll << 20;
+constexpr int64_t kSliceBudget = 2 * kCacheBytes;
+constexpr int64_t kMinSliceRow = 256;
+constexpr int kPlanFirstSliced = 1;
+
+extern "C" int mjx_rollout_ell_rp_plan(int64_t n, int d, int64_t words, int steps, int* slices, int* slice_major,
+                                       int* first_sliced) {
+    if (n < 0 || d < 0 || d > 255 || words < 1 || !slices || !slice_major || !first_sliced) return MJX_EINVAL;
+    *slices = 1; *slice_major = 0; *first_sliced = 0;
+    const int64_t adj_bytes = n * d * 4, state = n * words * 8;
+    if (kSliceBudget <= 0 || steps < 2 || state + adj_bytes <= kCacheBytes) return MJX_OK;
+    const int64_t U = units_of(words);
+    for (int64_t S = 2; S <= U; ++S) {
+        if (U % S) continue;
+        const int64_t row = words / S * 8, lines = (row + 127) / 128 * 128;
+        if (row < kMinSliceRow) break;
+        if (n * (row + lines) + adj_bytes <= kSliceBudget) {
+            *slices = (int)S; *slice_major = 1; *first_sliced = kPlanFirstSliced;
+            return MJX_OK;
+        }
+    }
+    return MJX_OK;
+}
+
+static int check_rollout_ell_rp(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
+                                uint64_t* s_out, uint64_t* tmp, int steps, int slices) {
     if (n < 0 || d < 0 || d > 255 || words < 1 || slices < 0 || (n > 0 && (!s_in || !s_out || (!adj && d > 0))))
         return MJX_EINVAL;
     if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
     if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
+    if (steps < 0) return MJX_EINVAL;
+    return MJX_OK;
+}
+
+extern "C" int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
+                                         uint64_t* s_out, uint64_t* tmp, int steps, int slices,
+                                         unsigned long long* counts, void* stream) {
+    int rc = check_rollout_ell_rp(adj, n, d, words, s_in, s_out, tmp, steps, slices);
+    if (rc) return rc;
     if (n == 0) return MJX_OK;
     hipStream_t st = as_stream(stream);
     const size_t bytes = (size_t)n * (size_t)words * 8;
-    if (steps < 0) return MJX_EINVAL;
     if (steps == 0) {
         MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, st), "rollout copy");
         return counts ? mjx_popcount_rp(s_out, n, words, counts, stream) : MJX_OK;
     }
     const int64_t U = units_of(words);
-    const int S = slices ? slices : auto_slices(n, words);
+    int S = slices;
+    if (!S) {
+        int sm = 0, fs = 0;
+        rc = mjx_rollout_ell_rp_plan(n, d, words, steps, &S, &sm, &fs);
+        if (rc) return rc;
+        if (sm) return mjx_rollout_ell_rp_sm(adj, n, d, words, s_in, s_out, tmp, steps, S, fs, counts, stream);
+    }
     if (S < 1 || U % S) return MJX_EINVAL;
     const int64_t Us = U / S;
     for (int q = 0; q < S; ++q) {
         auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {
             return launch_sweep_ell_rp(adj, n, d, words, a, b, c, q * Us, Us, st);
         };
-        int rc = run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
+        rc = run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
+        if (rc) return rc;
+    }
+    return MJX_OK;
+}
+
+// The rollout over a slice-major intermediate state (include/mjx.h).  Slice q's
+// region of a slice-major buffer is the n rows of ws = words/S words at
+// buffer + q*n*ws.
+//   first_sliced == 0: the first sweep is one launch over whole node-major rows
+//     that writes every slice's region; the later sweeps run slice by slice,
+//     sweep after sweep, ping-ponging between tmp and s_out (both slice-major
+//     until the last sweep writes s_out's node-major pieces from tmp).
+//   first_sliced != 0: slice by slice, the slice's whole chain at once: node-major
+//     pieces of s_in -> region A -> region B -> ... -> node-major pieces of s_out,
+//     A and B the first two regions of tmp (S >= 2).
+extern "C" int mjx_rollout_ell_rp_sm(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
+                                     uint64_t* s_out, uint64_t* tmp, int steps, int slices, int first_sliced,
+                                     unsigned long long* counts, void* stream) {
+    int rc = check_rollout_ell_rp(adj, n, d, words, s_in, s_out, tmp, steps, slices);
+    if (rc) return rc;
+    const int64_t U = units_of(words);
+    if (slices < 1 || U % slices) return MJX_EINVAL;
+    // nothing to keep between sweeps, or nothing to slice: the node-major path
+    if (n == 0 || steps < 2 || slices == 1)
+        return mjx_rollout_ell_rp_sliced(adj, n, d, words, s_in, s_out, tmp, steps, slices, counts, stream);
+    if (!tmp) return MJX_EINVAL;
+    hipStream_t st = as_stream(stream);
+    const int S = slices;
+    const int64_t Us = U / S, ws = words / S, region = n * ws;
+    const u64* in = (const u64*)s_in;
+    u64 *out = (u64*)s_out, *scratch = (u64*)tmp;
+    const SliceGeom to_slices{0, 1, ws, Us}, in_slices{ws, Us, ws, Us}, from_slices{ws, Us, 0, 1};
+    if (!first_sliced) {
+        auto buf = [&](int k) { return (((steps - 1 - k) & 1) == 0) ? out : scratch; };   // sweep k's output
+        rc = launch_sweep_ell_rp_v(adj, n, d, words, in, kNodeRows, buf(0), kSliceRows, to_slices, nullptr, 0, U, st);
+        if (rc) return rc;
+        for (int k = 1; k < steps - 1; ++k)
+            for (int q = 0; q < S; ++q) {
+                rc = launch_sweep_ell_rp_v(adj, n, d, words, buf(k - 1) + q * region, kSliceRows,
+                                           buf(k) + q * region, kSliceRows, in_slices, nullptr, q * Us, Us, st);
+                if (rc) return rc;
+            }
+        for (int q = 0; q < S; ++q) {
+            rc = launch_sweep_ell_rp_v(adj, n, d, words, scratch + q * region, kSliceRows, out, kNodeRows,
+                                       from_slices, counts, q * Us, Us, st);
+            if (rc) return rc;
+        }
+        return MJX_OK;
+    }
+    u64* ab[2] = {scratch, scratch + region};
+    for (int q = 0; q < S; ++q) {
+        rc = launch_sweep_ell_rp_v(adj, n, d, words, in, kNodeRows, ab[0], kSliceRows, to_slices, nullptr, q * Us, Us,
+                                   st);
+        if (rc) return rc;
+        for (int k = 1; k < steps - 1; ++k) {
+            rc = launch_sweep_ell_rp_v(adj, n, d, words, ab[(k - 1) & 1], kSliceRows, ab[k & 1], kSliceRows,
+                                       in_slices, nullptr, q * Us, Us, st);
+            if (rc) return rc;
+        }
+        rc = launch_sweep_ell_rp_v(adj, n, d, words, ab[(steps - 2) & 1], kSliceRows, out, kNodeRows, from_slices,
+                                   counts, q * Us, Us, st);
         if (rc) return rc;
     }
     return MJX_OK;
@@ -1628,7 +1805,7 @@ extern "C" int mjx_rollout_csr_rp_ordered(const int64_t* row_ptr, const int32_t*
         return counts ? mjx_popcount_rp(s_out, n, words, counts, stream) : MJX_OK;
     }
     const int64_t U = units_of(words);
-    const int S = auto_slices(n, words);
+    const int S = 1;                                   // the CSR rollout is not sliced
     const int64_t Us = U / S;
     for (int q = 0; q < S; ++q) {
         auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {

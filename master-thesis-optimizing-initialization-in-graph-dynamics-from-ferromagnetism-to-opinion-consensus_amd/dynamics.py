@@ -54,15 +54,21 @@ def unpack(bits, n, R=None, dtype=torch.int64):
     return s
 
 
-def rollout(graph, bits, steps, words=None, out=None, tmp=None, counts=None, slices=None):
+def rollout(graph, bits, steps, words=None, out=None, tmp=None, counts=None, slices=None, layout="node",
+            first_sliced=False):
     """Apply ``steps`` synchronous majority sweeps to packed spins.
 
     words=None: node-packed single replica; else replica-packed with ``words``
     64-bit words per node.  ``counts`` (uint64 tensor viewed as int64, length
     R or 1) receives, added, the number of +1 spins of the result.
     ``slices`` (ELL, replica-packed only): run the replicas in that many
-    slices (mjx_rollout_ell_rp_sliced); None = the library's automatic choice.
+    slices (mjx_rollout_ell_rp_sliced); None = the library's automatic choice
+    (mjx_rollout_ell_rp_plan).  With ``slices``, ``layout="slice"`` keeps the
+    states between the sweeps slice-major (mjx_rollout_ell_rp_sm) and
+    ``first_sliced`` picks its first-sweep variant; the result is the same.
     """
+    if layout not in ("node", "slice"):
+        raise ValueError("layout must be 'node' or 'slice'")
     st = _device.stream_handle()
     out = torch.empty_like(bits) if out is None else out
     if steps >= 2 and tmp is None:
@@ -73,6 +79,10 @@ def rollout(graph, bits, steps, words=None, out=None, tmp=None, counts=None, sli
         if words is None:
             _lib.call("mjx_rollout_ell_np", _device.ptr(graph.adj), graph.n, graph.d, _device.ptr(bits),
                       _device.ptr(out), tptr, int(steps), cptr, st)
+        elif layout == "slice" and slices:
+            _lib.call("mjx_rollout_ell_rp_sm", _device.ptr(graph.adj), graph.n, graph.d, int(words),
+                      _device.ptr(bits), _device.ptr(out), tptr, int(steps), int(slices), int(bool(first_sliced)),
+                      cptr, st)
         else:
             _lib.call("mjx_rollout_ell_rp_sliced", _device.ptr(graph.adj), graph.n, graph.d, int(words),
                       _device.ptr(bits), _device.ptr(out), tptr, int(steps), int(slices or 0), cptr, st)
