@@ -12,6 +12,7 @@
 #include "mjx_common.h"
 #include "mjx_philox.h"
 #include <algorithm>
+#include <type_traits>
 #include <string.h>
 #include <stdio.h>
 #include <mutex>
@@ -456,52 +457,80 @@ __device__ __forceinline__ void stv(u64* __restrict__ p, const u64* x) {
     }
 }
 
-// A launch covers the units [unit0, unit0 + Us) of every node (a "slice" of
-// the replicas); LDS counters are indexed relative to the slice.
-template <int VW, int NK>
-__device__ __forceinline__ void flush_to(VertCounter<VW, NK>& vc, int use_lds, unsigned* lds,
-                                         unsigned long long* counts, int64_t unit, int64_t unit0) {
-    if (use_lds) vc.flush(lds + (unit - unit0) * VW * 64, (int)((unit - unit0) & 63));
-    else vc.flush(counts + unit * VW * 64);
-}
-
-template <int VW, int BS = kBlock>
-__device__ __forceinline__ void lds_count_init(unsigned* lds, int64_t Us, bool use_lds) {
-    if (use_lds) {
-        for (int64_t r = threadIdx.x; r < Us * VW * 64; r += BS) lds[r] = 0;
-        __syncthreads();
+// The thread frame of a launch over the units [unit0, unit0 + Us) of every
+// node (a "slice" of the replicas): thread t owns unit unit0 + t % Us of the
+// items slot, slot + slots, ...; a thread past the last whole slot is idle
+// (and still reaches the block's barriers).
+struct Frame {
+    int64_t unit0, Us, unit, slot, slots;
+    bool active;
+    __device__ __forceinline__ Frame(int64_t Us_, int64_t unit0_ = 0) : unit0(unit0_), Us(Us_) {
+        const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+        slots = ((int64_t)gridDim.x * kBlock) / Us;
+        unit = unit0 + t % Us;
+        slot = t / Us;
+        active = slot < slots;
     }
-}
+};
 
-// Shared epilogue for the fused per-replica counts.
-template <int VW, bool COUNT, int BS = kBlock, int NK = KC>
-__device__ __forceinline__ void count_epilogue(VertCounter<VW, NK>& vc, bool active, int64_t unit, int64_t unit0,
-                                               int64_t Us, unsigned* lds, bool use_lds,
-                                               unsigned long long* __restrict__ counts) {
-    if constexpr (COUNT) {
-        if (use_lds) {
-            if (active && vc.added) vc.flush(lds + (unit - unit0) * VW * 64, (int)((unit - unit0) & 63));
-            __syncthreads();  // every thread of the block reaches this (no early return)
-            // undo the bank rotation; blocks start their walk at different
-            // replicas so that blocks ending together do not queue their global
-            // atomics on the same addresses
-            const int64_t r0 = unit0 * VW * 64, tot = Us * VW * 64;
-            const int64_t start = ((int64_t)blockIdx.x * BS) % tot;
-            for (int64_t i = threadIdx.x; i < tot; i += BS) {
-                int64_t r = start + i;
-                if (r >= tot) r -= tot;
-                const unsigned x = lds[r];
-                if (x) {
-                    const int64_t u = r / (VW * 64), rem = r - u * (VW * 64);
-                    const int64_t b = ((rem & 63) - u) & 63;
-                    atomicAdd(&counts[r0 + u * (VW * 64) + (rem & ~63LL) + b], (unsigned long long)x);
-                }
+// The fused per-replica counts of a launch (nothing when !COUNT): the thread's
+// vertical counter, flushed when full and at the end into the block's LDS
+// counters (use_lds; indexed relative to the slice) or straight into `counts`.
+// (A 1024-thread counting block, 4x fewer global count atomics, measured
+// slower on MI355X: 537 vs 508 us at the bench size.)
+template <int VW, bool COUNT, int NK = KC>
+struct UnitCount {
+    VertCounter<VW, NK> vc;
+    unsigned* lds;
+    unsigned long long* counts;
+    bool use_lds;
+
+    __device__ __forceinline__ UnitCount(const Frame& f, unsigned* lds_, unsigned long long* counts_, int use_lds_)
+        : lds(lds_), counts(counts_), use_lds(use_lds_ != 0) {
+        if constexpr (COUNT) {
+            vc.reset();
+            if (use_lds) {
+                for (int64_t r = threadIdx.x; r < f.Us * VW * 64; r += kBlock) lds[r] = 0;
+                __syncthreads();
             }
-        } else {
-            if (active && vc.added) vc.flush(counts + unit * VW * 64);
         }
     }
-}
+    __device__ __forceinline__ void flush(const Frame& f) {
+        const int64_t u = f.unit - f.unit0;
+        if (use_lds) vc.flush(lds + u * VW * 64, (int)(u & 63));
+        else vc.flush(counts + f.unit * VW * 64);
+    }
+    __device__ __forceinline__ void add(const Frame& f, const u64* out) {
+        if constexpr (COUNT) {
+            vc.add(out);
+            if (vc.added == (1 << NK) - 1) flush(f);
+        }
+    }
+    // every thread of the block calls this (no early return before it)
+    __device__ __forceinline__ void finish(const Frame& f) {
+        if constexpr (COUNT) {
+            if (f.active && vc.added) flush(f);
+            if (use_lds) {
+                __syncthreads();
+                // undo the bank rotation; blocks start their walk at different
+                // replicas so that blocks ending together do not queue their global
+                // atomics on the same addresses
+                const int64_t r0 = f.unit0 * VW * 64, tot = f.Us * VW * 64;
+                const int64_t start = ((int64_t)blockIdx.x * kBlock) % tot;
+                for (int64_t i = threadIdx.x; i < tot; i += kBlock) {
+                    int64_t r = start + i;
+                    if (r >= tot) r -= tot;
+                    const unsigned x = lds[r];
+                    if (x) {
+                        const int64_t u = r / (VW * 64), rem = r - u * (VW * 64);
+                        const int64_t b = ((rem & 63) - u) & 63;
+                        atomicAdd(&counts[r0 + u * (VW * 64) + (rem & ~63LL) + b], (unsigned long long)x);
+                    }
+                }
+            }
+        }
+    }
+};
 
 // Row views of a launch's state arrays.  The input and the output of a sweep
 // each have their own:
@@ -543,341 +572,229 @@ __device__ __forceinline__ T* row_at(T* __restrict__ p, int64_t v, int64_t W, in
     if constexpr (KIND == kNodeRows) return p + v * W + unit * VW;
     else return p + v * ws + soff;
 }
-
-// BS: block size (a 1024-thread counting sweep, 4x fewer global count atomics,
-// measured slower on MI355X: 537 vs 508 us at the bench size -- kept at 256).
-template <int D, int VW, bool COUNT, int BS = kBlock, int IK = kNodeRows, int OK = kNodeRows>
-__global__ void __launch_bounds__(BS) k_sweep_ell_rp(const int32_t* __restrict__ adj, int64_t n, int64_t W,
-                                                     const u64* __restrict__ s_in, u64* __restrict__ s_out,
-                                                     unsigned long long* __restrict__ counts, int use_lds,
-                                                     int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga) {
-    extern __shared__ unsigned lds_cnt[];
-    const SliceGeom sg = ga.get();
-    const int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * BS) / Us;
-    const int64_t unit = unit0 + t % Us, slot = t / Us;
-    const bool active = slot < slots;
-    const int64_t ioff = slice_off<IK, VW>(n, unit, unit0, sg.in_ws, sg.in_us);
-    const int64_t ooff = slice_off<OK, VW>(n, unit, unit0, sg.out_ws, sg.out_us);
-    VertCounter<VW> vc;
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW, BS>(lds_cnt, Us, use_lds);
-    }
-    if (active) {
-        for (int64_t v = slot; v < n; v += slots) {
-            int32_t k[D];
-            load_adj<D>(adj, v, k);
-            u64 x[D][VW], own[VW], out[VW];
-#pragma unroll
-            for (int j = 0; j < D; ++j) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[j], W, unit, sg.in_ws, ioff), x[j]);
-            ldv<VW>(row_at<IK, VW>(s_in, v, W, unit, sg.in_ws, ioff), own);
-#pragma unroll
-            for (int q = 0; q < VW; ++q) {
-                u64 xs[D];
-#pragma unroll
-                for (int j = 0; j < D; ++j) xs[j] = x[j][q];
-                out[q] = majority_fixed<D>(xs, own[q]);
-            }
-            stv<VW>(row_at<OK, VW>(s_out, v, W, unit, sg.out_ws, ooff), out);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
-            }
-        }
-    }
-    count_epilogue<VW, COUNT, BS>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
-}
-
-// runtime degree (ELL rows of length d) and CSR rows; KB counter planes
-template <int VW, bool COUNT, bool CSR, int IK = kNodeRows, int OK = kNodeRows>
-__global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restrict__ adj, int d,
-                                                         const int64_t* __restrict__ row_ptr,
-                                                         const int32_t* __restrict__ col,
-                                                         const int32_t* __restrict__ order, int64_t n, int64_t W,
-                                                         const u64* __restrict__ s_in, u64* __restrict__ s_out,
-                                                         unsigned long long* __restrict__ counts, int use_lds,
-                                                         int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga) {
-    const SliceGeom sg = ga.get();
-    // order (nullable): node visiting order; sorted by degree it keeps the two
-    // nodes a wave holds at one trip count (irregular ER rows)
-    extern __shared__ unsigned lds_cnt[];
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = unit0 + t % Us, slot = t / Us;
-    const bool active = slot < slots;
-    const int64_t ioff = slice_off<IK, VW>(n, unit, unit0, sg.in_ws, sg.in_us);
-    const int64_t ooff = slice_off<OK, VW>(n, unit, unit0, sg.out_ws, sg.out_us);
-    VertCounter<VW, 10> vc;     // up to 1023 nodes per thread between flushes (N = 1e7 rows)
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW>(lds_cnt, Us, use_lds);
-    }
-    if (active) {
-        for (int64_t i = slot; i < n; i += slots) {
-            const int64_t v = order ? (int64_t)order[i] : i;
-            int64_t b, e;
-            const int32_t* nbr;
-            if constexpr (CSR) {
-                b = row_ptr[v]; e = row_ptr[v + 1]; nbr = col;
-            } else {
-                b = v * d; e = b + d; nbr = adj;
-            }
-            const int deg = (int)(e - b);
-            BitCounter<8> bc[VW];
-#pragma unroll
-            for (int q = 0; q < VW; ++q) bc[q].reset();
-            // four gathers in flight per step (rows have d = 5 on average at C4)
-            int64_t j = b;
-            for (; j + 4 <= e; j += 4) {
-                int32_t k[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) k[m] = nbr[j + m];
-                u64 x[4][VW];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[m], W, unit, sg.in_ws, ioff), x[m]);
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
-            }
-            if (j < e) {
-                const int rest = (int)(e - j);
-                int32_t k[3];
-#pragma unroll
-                for (int m = 0; m < 3; ++m) k[m] = m < rest ? nbr[j + m] : 0;
-                u64 x[3][VW];
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-                    if (m < rest) ldv<VW>(row_at<IK, VW>(s_in, (int64_t)k[m], W, unit, sg.in_ws, ioff), x[m]);
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-                    if (m < rest)
-#pragma unroll
-                        for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
-            }
-            u64 own[VW], out[VW];
-            ldv<VW>(row_at<IK, VW>(s_in, v, W, unit, sg.in_ws, ioff), own);
-#pragma unroll
-            for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(deg, own[q]);
-            stv<VW>(row_at<OK, VW>(s_out, v, W, unit, sg.out_ws, ooff), out);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << decltype(vc)::KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
-            }
-        }
-    }
-    count_epilogue<VW, COUNT, kBlock, 10>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
-}
-
-// ---------------------------------------------------------------------------
-// Tracked replica-packed sweeps (run to the attractor, include/mjx.h): one
-// step of the sweeps above that also reports, per replica, whether any node
-// changed against s_in ("s(t+1) != s(t)": the own word is already in
-// registers) and against s_prev ("s(t+1) != s(t-1)": one more streamed word
-// per node, the very word a ping-pong sweep overwrites -- s_out may be
-// s_prev; the thread that owns (node, unit) loads it before it stores).
-// A thread's replica range is fixed, so it ORs out ^ own and out ^ prev into
-// 2*VW registers over its nodes; the block ORs them in LDS and issues one
-// global atomicOr per non-zero flag word.  Sibling kernels: the sweeps above
-// are not touched, so the untracked rollouts compile to the code they had.
-// Dynamic LDS: the fused counters (Us*VW*64 unsigned, when use_lds), then
-// 2*Us*VW flag words (when use_dlds; else Us >= block size, every thread of a
-// block owns another unit and ORs its words into `diff` itself).
-// ---------------------------------------------------------------------------
-template <int VW>
-struct DiffAcc {
-    u64 in[VW], prev[VW];      // ORs of out ^ own and of out ^ prev
-    __device__ __forceinline__ void reset() {
-#pragma unroll
-        for (int q = 0; q < VW; ++q) in[q] = prev[q] = 0;
-    }
-    __device__ __forceinline__ void add(const u64* out, const u64* own) {
-#pragma unroll
-        for (int q = 0; q < VW; ++q) in[q] |= out[q] ^ own[q];
-    }
-    __device__ __forceinline__ void add_prev(const u64* out, const u64* pv) {
-#pragma unroll
-        for (int q = 0; q < VW; ++q) prev[q] |= out[q] ^ pv[q];
-    }
+// a thread's view of a state array: rows(v) = node v's words of the thread's unit
+template <int KIND, int VW, typename T>
+struct Rows {
+    T* p;
+    int64_t W, unit, ws, off;
+    // n, ws, us: the slice-major geometry (unused by a node-major view)
+    __device__ __forceinline__ Rows(T* p_, int64_t W_, const Frame& f, int64_t n = 0, int64_t ws_ = 0, int64_t us = 1)
+        : p(p_), W(W_), unit(f.unit), ws(ws_), off(slice_off<KIND, VW>(n, f.unit, f.unit0, ws_, us)) {}
+    __device__ __forceinline__ T* operator()(int64_t v) const { return row_at<KIND, VW>(p, v, W, unit, ws, off); }
 };
+template <int VW> using NodeRows = Rows<kNodeRows, VW, const u64>;
 
-__device__ __forceinline__ u64* diff_lds(unsigned* lds, int use_lds, int64_t Us, int VW) {
-    return reinterpret_cast<u64*>(lds + (use_lds ? Us * VW * 64 : 0));   // 8-byte aligned: VW*64 unsigneds a unit
-}
-
-template <int VW>
-__device__ __forceinline__ void diff_init(u64* dl, int64_t Us, int use_dlds) {
-    if (use_dlds) {
-        for (int64_t i = threadIdx.x; i < 2 * Us * VW; i += kBlock) dl[i] = 0;
-        __syncthreads();
-    }
-}
-
-// diff[0 .. W): changed against s_in; diff[W .. 2W): against s_prev (has_prev)
-template <int VW, typename DST>
-__device__ __forceinline__ void diff_or(const DiffAcc<VW>& da, bool has_prev, DST* first, DST* second) {
-#pragma unroll
-    for (int q = 0; q < VW; ++q)
-        if (da.in[q]) atomicOr(&first[q], da.in[q]);
-    if (has_prev) {
-#pragma unroll
-        for (int q = 0; q < VW; ++q)
-            if (da.prev[q]) atomicOr(&second[q], da.prev[q]);
-    }
-}
-
-template <int VW>
-__device__ __forceinline__ void diff_epilogue(const DiffAcc<VW>& da, bool active, bool has_prev, int64_t unit,
-                                              int64_t unit0, int64_t Us, int64_t W, u64* dl, int use_dlds,
-                                              u64* __restrict__ diff) {
-    if (use_dlds) {
-        if (active) diff_or<VW>(da, has_prev, dl + (unit - unit0) * VW, dl + (Us + unit - unit0) * VW);
-        __syncthreads();  // every thread of the block reaches this (no early return)
-        const int64_t tot = (has_prev ? 2 : 1) * Us * VW;
-        for (int64_t i = threadIdx.x; i < tot; i += kBlock) {
-            const u64 x = dl[i];
-            if (x) {
-                const int64_t h = i / (Us * VW), w = i - h * (Us * VW);
-                atomicOr(&diff[h * W + unit0 * VW + w], x);
-            }
-        }
-    } else if (active) {
-        diff_or<VW>(da, has_prev, diff + unit * VW, diff + W + unit * VW);
-    }
-}
-
-template <int D, int VW, bool COUNT>
-__global__ void __launch_bounds__(kBlock) k_sweep_track_ell_rp(const int32_t* __restrict__ adj, int64_t n, int64_t W,
-                                                               const u64* __restrict__ s_in, const u64* s_prev,
-                                                               u64* s_out, unsigned long long* __restrict__ counts,
-                                                               int use_lds, u64* __restrict__ diff, int use_dlds,
-                                                               int64_t unit0, int64_t Us) {
-    extern __shared__ unsigned lds_cnt[];
-    u64* const dl = diff_lds(lds_cnt, COUNT ? use_lds : 0, Us, VW);
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = unit0 + t % Us, slot = t / Us;
-    const bool active = slot < slots, has_prev = s_prev != nullptr;
-    VertCounter<VW> vc;
-    DiffAcc<VW> da;
-    da.reset();
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW>(lds_cnt, Us, use_lds);
-    }
-    diff_init<VW>(dl, Us, use_dlds);
-    if (active) {
-        for (int64_t v = slot; v < n; v += slots) {
-            int32_t k[D];
-            load_adj<D>(adj, v, k);
-            u64 x[D][VW], own[VW], prev[VW], out[VW];
-#pragma unroll
-            for (int j = 0; j < D; ++j) ldv<VW>(s_in + (int64_t)k[j] * W + unit * VW, x[j]);
-            ldv<VW>(s_in + v * W + unit * VW, own);
-            if (has_prev) ldv<VW>(s_prev + v * W + unit * VW, prev);
-#pragma unroll
-            for (int q = 0; q < VW; ++q) {
-                u64 xs[D];
-#pragma unroll
-                for (int j = 0; j < D; ++j) xs[j] = x[j][q];
-                out[q] = majority_fixed<D>(xs, own[q]);
-            }
-            stv<VW>(s_out + v * W + unit * VW, out);
-            da.add(out, own);
-            if (has_prev) da.add_prev(out, prev);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
-            }
-        }
-    }
-    count_epilogue<VW, COUNT>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
-    diff_epilogue<VW>(da, active, has_prev, unit, unit0, Us, W, dl, use_dlds, diff);
-}
-
-// the new bits of this thread's unit of node v, rows of runtime length
-// (ELL rows of length d, or CSR rows): the node body of k_sweep_gen_rp
-template <int VW, bool CSR>
-__device__ __forceinline__ void gen_node(const int32_t* __restrict__ adj, int d, const int64_t* __restrict__ row_ptr,
-                                         const int32_t* __restrict__ col, int64_t v, int64_t W,
-                                         const u64* __restrict__ s_in, int64_t unit, u64* own, u64* out) {
-    int64_t b, e;
-    const int32_t* nbr;
-    if constexpr (CSR) {
-        b = row_ptr[v]; e = row_ptr[v + 1]; nbr = col;
-    } else {
-        b = v * d; e = b + d; nbr = adj;
-    }
-    const int deg = (int)(e - b);
+// The new bits `out` of the thread's unit of node v, read through the view
+// `in` (and the node's own words, which the tracked sweeps compare), for a row
+// of runtime degree (an ELL row of length d, a CSR row, a class row above D = 8):
+// the neighbours are row[0 .. deg), deg <= 255 (BitCounter<8>).  Four gathers
+// in flight per step (rows have d = 5 on average at C4), then the rest of the
+// row one neighbour at a time (a masked step of three measured 3-6 % faster on
+// CSR rows and 1 % slower on rows of length 5: DESIGN.md).
+template <int VW, typename IN>
+__device__ __forceinline__ void row_node(const int32_t* __restrict__ row, int deg, int64_t v, const IN& in, u64* own,
+                                         u64* out) {
     BitCounter<8> bc[VW];
 #pragma unroll
     for (int q = 0; q < VW; ++q) bc[q].reset();
-    int64_t j = b;
-    for (; j + 4 <= e; j += 4) {
+    int j = 0;
+    for (; j + 4 <= deg; j += 4) {
         int32_t k[4];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) k[m] = nbr[j + m];
+        for (int m = 0; m < 4; ++m) k[m] = row[j + m];
         u64 x[4][VW];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
+        for (int m = 0; m < 4; ++m) ldv<VW>(in((int64_t)k[m]), x[m]);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
     }
-    for (; j < e; ++j) {
+    for (; j < deg; ++j) {
         u64 x[VW];
-        ldv<VW>(s_in + (int64_t)nbr[j] * W + unit * VW, x);
+        ldv<VW>(in((int64_t)row[j]), x);
 #pragma unroll
         for (int q = 0; q < VW; ++q) bc[q].add(x[q]);
     }
-    ldv<VW>(s_in + v * W + unit * VW, own);
+    ldv<VW>(in(v), own);
 #pragma unroll
     for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(deg, own[q]);
 }
 
-template <int VW, bool COUNT, bool CSR>
-__global__ void __launch_bounds__(kBlock) k_sweep_track_gen_rp(const int32_t* __restrict__ adj, int d,
-                                                               const int64_t* __restrict__ row_ptr,
-                                                               const int32_t* __restrict__ col,
-                                                               const int32_t* __restrict__ order, int64_t n,
-                                                               int64_t W, const u64* __restrict__ s_in,
-                                                               const u64* s_prev, u64* s_out,
-                                                               unsigned long long* __restrict__ counts, int use_lds,
-                                                               u64* __restrict__ diff, int use_dlds, int64_t unit0,
-                                                               int64_t Us) {
-    extern __shared__ unsigned lds_cnt[];
-    u64* const dl = diff_lds(lds_cnt, COUNT ? use_lds : 0, Us, VW);
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = unit0 + t % Us, slot = t / Us;
-    const bool active = slot < slots, has_prev = s_prev != nullptr;
-    VertCounter<VW, 10> vc;
-    DiffAcc<VW> da;
-    da.reset();
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW>(lds_cnt, Us, use_lds);
-    }
-    diff_init<VW>(dl, Us, use_dlds);
-    if (active) {
-        for (int64_t i = slot; i < n; i += slots) {
-            const int64_t v = order ? (int64_t)order[i] : i;
-            u64 own[VW], prev[VW], out[VW];
-            if (has_prev) ldv<VW>(s_prev + v * W + unit * VW, prev);
-            gen_node<VW, CSR>(adj, d, row_ptr, col, v, W, s_in, unit, own, out);
-            stv<VW>(s_out + v * W + unit * VW, out);
-            da.add(out, own);
-            if (has_prev) da.add_prev(out, prev);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << decltype(vc)::KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
+// Tracked sweeps (TRACK; run to the attractor, include/mjx.h): one step of a
+// sweep that also reports, per replica, whether any node changed against s_in
+// ("s(t+1) != s(t)": the own word is already in registers) and against s_prev
+// ("s(t+1) != s(t-1)": one more streamed word per node, the very word a
+// ping-pong sweep overwrites -- s_out may be s_prev, so a tracked sweep's
+// s_out carries no __restrict__; the thread that owns (node, unit) loads the
+// word before it stores).  A thread's replica range is fixed, so it ORs
+// out ^ own and out ^ prev into 2*VW registers over its nodes; the block ORs
+// them in LDS and issues one global atomicOr per non-zero flag word.
+// Dynamic LDS: the fused counters (Us*VW*64 unsigned, when use_lds), then
+// 2*Us*VW flag words (when use_dlds; else Us >= block size, every thread of a
+// block owns another unit and ORs its words into `diff` itself).
+// The tracked sweeps' kernel arguments: none for a plain sweep.
+template <bool TRACK> struct TrackArg {
+    const u64* s_prev;         // nullable: no "against s_prev" half
+    u64* diff;                 // diff[0 .. W): changed against s_in; diff[W .. 2W): against s_prev
+    int use_dlds;
+};
+template <> struct TrackArg<false> {};
+template <bool TRACK> using OutPtr = std::conditional_t<TRACK, u64*, u64* __restrict__>;
+
+template <int VW, bool TRACK>
+struct DiffTrack {
+    TrackArg<TRACK> a;
+    u64 in[VW], prev[VW];      // ORs of out ^ own and of out ^ prev over the thread's nodes
+    u64* dl;                   // the block's flag words in LDS, behind the counters (8-byte aligned: VW*64 unsigneds a unit)
+
+    __device__ __forceinline__ DiffTrack(const Frame& f, unsigned* lds, int counters_in_lds, const TrackArg<TRACK>& a_)
+        : a(a_) {
+        if constexpr (TRACK) {
+            dl = reinterpret_cast<u64*>(lds + (counters_in_lds ? f.Us * VW * 64 : 0));
+#pragma unroll
+            for (int q = 0; q < VW; ++q) in[q] = prev[q] = 0;
+            if (a.use_dlds) {
+                for (int64_t i = threadIdx.x; i < 2 * f.Us * VW; i += kBlock) dl[i] = 0;
+                __syncthreads();
             }
         }
     }
-    count_epilogue<VW, COUNT, kBlock, 10>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
-    diff_epilogue<VW>(da, active, has_prev, unit, unit0, Us, W, dl, use_dlds, diff);
+    // node v's words of s_prev: before the store of its new words
+    __device__ __forceinline__ void load_prev(const Frame& f, int64_t v, int64_t W, u64* pv) const {
+        if constexpr (TRACK)
+            if (a.s_prev) ldv<VW>(a.s_prev + v * W + f.unit * VW, pv);
+    }
+    __device__ __forceinline__ void add(const u64* out, const u64* own, const u64* pv) {
+        if constexpr (TRACK) {
+#pragma unroll
+            for (int q = 0; q < VW; ++q) in[q] |= out[q] ^ own[q];
+            if (a.s_prev) {
+#pragma unroll
+                for (int q = 0; q < VW; ++q) prev[q] |= out[q] ^ pv[q];
+            }
+        }
+    }
+    template <typename DST>
+    __device__ __forceinline__ void or_into(DST* first, DST* second) const {
+#pragma unroll
+        for (int q = 0; q < VW; ++q)
+            if (in[q]) atomicOr(&first[q], in[q]);
+        if (a.s_prev) {
+#pragma unroll
+            for (int q = 0; q < VW; ++q)
+                if (prev[q]) atomicOr(&second[q], prev[q]);
+        }
+    }
+    // every thread of the block calls this (no early return before it)
+    __device__ __forceinline__ void finish(const Frame& f, int64_t W) const {
+        if constexpr (TRACK) {
+            if (a.use_dlds) {
+                if (f.active) or_into(dl + (f.unit - f.unit0) * VW, dl + (f.Us + f.unit - f.unit0) * VW);
+                __syncthreads();
+                const int64_t tot = (a.s_prev ? 2 : 1) * f.Us * VW;
+                for (int64_t i = threadIdx.x; i < tot; i += kBlock) {
+                    const u64 x = dl[i];
+                    if (x) {
+                        const int64_t h = i / (f.Us * VW), w = i - h * (f.Us * VW);
+                        atomicOr(&a.diff[h * W + f.unit0 * VW + w], x);
+                    }
+                }
+            } else if (f.active) {
+                or_into(a.diff + f.unit * VW, a.diff + W + f.unit * VW);
+            }
+        }
+    }
+};
+
+// TRACK is instantiated with node-major views only.
+template <int D, int VW, bool COUNT, int IK = kNodeRows, int OK = kNodeRows, bool TRACK = false>
+__global__ void __launch_bounds__(kBlock) k_sweep_ell_rp(const int32_t* __restrict__ adj, int64_t n, int64_t W,
+                                                         const u64* __restrict__ s_in, OutPtr<TRACK> s_out,
+                                                         unsigned long long* __restrict__ counts, int use_lds,
+                                                         int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga,
+                                                         TrackArg<TRACK> ta) {
+    extern __shared__ unsigned lds_cnt[];
+    const SliceGeom sg = ga.get();
+    const Frame f(Us, unit0);
+    const Rows<IK, VW, const u64> in(s_in, W, f, n, sg.in_ws, sg.in_us);
+    const Rows<OK, VW, u64> dst(s_out, W, f, n, sg.out_ws, sg.out_us);
+    UnitCount<VW, COUNT> uc(f, lds_cnt, counts, use_lds);
+    DiffTrack<VW, TRACK> trk(f, lds_cnt, COUNT ? use_lds : 0, ta);
+    if (f.active) {
+        for (int64_t v = f.slot; v < n; v += f.slots) {
+            int32_t k[D];
+            load_adj<D>(adj, v, k);
+            u64 x[D][VW], own[VW], prev[VW], out[VW];
+#pragma unroll
+            for (int j = 0; j < D; ++j) ldv<VW>(in((int64_t)k[j]), x[j]);
+            ldv<VW>(in(v), own);
+            trk.load_prev(f, v, W, prev);
+#pragma unroll
+            for (int q = 0; q < VW; ++q) {
+                u64 xs[D];
+#pragma unroll
+                for (int j = 0; j < D; ++j) xs[j] = x[j][q];
+                out[q] = majority_fixed<D>(xs, own[q]);
+            }
+            stv<VW>(dst(v), out);
+            trk.add(out, own, prev);
+            uc.add(f, out);
+        }
+    }
+    uc.finish(f);
+    trk.finish(f, W);
+}
+
+// a runtime-degree sweep's row of node v: ELL rows of length d, or CSR rows
+template <bool CSR>
+__device__ __forceinline__ const int32_t* gen_row(const int32_t* __restrict__ adj, int d,
+                                                  const int64_t* __restrict__ row_ptr,
+                                                  const int32_t* __restrict__ col, int64_t v, int* deg) {
+    if constexpr (CSR) {
+        const int64_t b = row_ptr[v];
+        *deg = (int)(row_ptr[v + 1] - b);
+        return col + b;
+    } else {
+        *deg = d;
+        return adj + v * d;
+    }
+}
+
+// runtime degree (ELL rows of length d) and CSR rows
+template <int VW, bool COUNT, bool CSR, int IK = kNodeRows, int OK = kNodeRows, bool TRACK = false>
+__global__ void __launch_bounds__(kBlock) k_sweep_gen_rp(const int32_t* __restrict__ adj, int d,
+                                                         const int64_t* __restrict__ row_ptr,
+                                                         const int32_t* __restrict__ col,
+                                                         const int32_t* __restrict__ order, int64_t n, int64_t W,
+                                                         const u64* __restrict__ s_in, OutPtr<TRACK> s_out,
+                                                         unsigned long long* __restrict__ counts, int use_lds,
+                                                         int64_t unit0, int64_t Us, GeomArg<(IK | OK) != 0> ga,
+                                                         TrackArg<TRACK> ta) {
+    // order (nullable): node visiting order; sorted by degree it keeps the two
+    // nodes a wave holds at one trip count (irregular ER rows)
+    extern __shared__ unsigned lds_cnt[];
+    const SliceGeom sg = ga.get();
+    const Frame f(Us, unit0);
+    const Rows<IK, VW, const u64> in(s_in, W, f, n, sg.in_ws, sg.in_us);
+    const Rows<OK, VW, u64> dst(s_out, W, f, n, sg.out_ws, sg.out_us);
+    UnitCount<VW, COUNT, 10> uc(f, lds_cnt, counts, use_lds);   // up to 1023 nodes per thread between flushes (N = 1e7 rows)
+    DiffTrack<VW, TRACK> trk(f, lds_cnt, COUNT ? use_lds : 0, ta);
+    if (f.active) {
+        for (int64_t i = f.slot; i < n; i += f.slots) {
+            const int64_t v = order ? (int64_t)order[i] : i;
+            int deg;
+            const int32_t* row = gen_row<CSR>(adj, d, row_ptr, col, v, &deg);
+            u64 own[VW], prev[VW], out[VW];
+            trk.load_prev(f, v, W, prev);
+            row_node<VW>(row, deg, v, in, own, out);
+            stv<VW>(dst(v), out);
+            trk.add(out, own, prev);
+            uc.add(f, out);
+        }
+    }
+    uc.finish(f);
+    trk.finish(f, W);
 }
 
 // Attractor bookkeeping after sweep k >= 2 (one thread a replica): a replica
@@ -952,20 +869,20 @@ __global__ void __launch_bounds__(kBlock) k_random_spins_rp(int64_t n, int64_t R
 // out[] and s_out.
 template <int D, int VW>
 __device__ __forceinline__ void cls_node(const int32_t* __restrict__ order, const int32_t* __restrict__ cell,
-                                         int64_t i, int dd, int64_t W, const u64* __restrict__ s_in,
-                                         u64* __restrict__ s_out, int64_t unit, u64* out) {
+                                         int64_t i, int dd, const NodeRows<VW>& in,
+                                         const Rows<kNodeRows, VW, u64>& dst, u64* out) {
     const int64_t v = order[i];
     u64 own[VW];
     if constexpr (D == 0) {
         // no neighbours: S = 0, a tie, the spin stays (nb:113-117)
-        ldv<VW>(s_in + v * W + unit * VW, out);
+        ldv<VW>(in(v), out);
     } else if constexpr (D > 0) {
         int32_t k[D];
         load_adj<D>(cell, i, k);
         u64 x[D][VW];
 #pragma unroll
-        for (int j = 0; j < D; ++j) ldv<VW>(s_in + (int64_t)k[j] * W + unit * VW, x[j]);
-        ldv<VW>(s_in + v * W + unit * VW, own);
+        for (int j = 0; j < D; ++j) ldv<VW>(in((int64_t)k[j]), x[j]);
+        ldv<VW>(in(v), own);
 #pragma unroll
         for (int q = 0; q < VW; ++q) {
             u64 xs[D];
@@ -974,34 +891,9 @@ __device__ __forceinline__ void cls_node(const int32_t* __restrict__ order, cons
             out[q] = majority_fixed<D>(xs, own[q]);
         }
     } else {
-        const int32_t* row = cell + i * dd;
-        BitCounter<8> bc[VW];
-#pragma unroll
-        for (int q = 0; q < VW; ++q) bc[q].reset();
-        int j = 0;
-        for (; j + 4 <= dd; j += 4) {
-            int32_t k[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) k[m] = row[j + m];
-            u64 x[4][VW];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
-        }
-        for (; j < dd; ++j) {
-            u64 x[VW];
-            ldv<VW>(s_in + (int64_t)row[j] * W + unit * VW, x);
-#pragma unroll
-            for (int q = 0; q < VW; ++q) bc[q].add(x[q]);
-        }
-        ldv<VW>(s_in + v * W + unit * VW, own);
-#pragma unroll
-        for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(dd, own[q]);
+        row_node<VW>(cell + i * dd, dd, v, in, own, out);
     }
-    stv<VW>(s_out + v * W + unit * VW, out);
+    stv<VW>(dst(v), out);
 }
 
 template <int D, int VW, bool COUNT, int NK = KC>
@@ -1010,28 +902,20 @@ __global__ void __launch_bounds__(kBlock) k_sweep_cls_rp(const int32_t* __restri
                                                          int64_t W, const u64* __restrict__ s_in,
                                                          u64* __restrict__ s_out,
                                                          unsigned long long* __restrict__ counts, int use_lds,
-                                                         int64_t unit0, int64_t Us) {
+                                                         int64_t Us) {
     extern __shared__ unsigned lds_cnt[];
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = unit0 + t % Us, slot = t / Us;
-    const bool active = slot < slots;
-    VertCounter<VW, NK> vc;
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW>(lds_cnt, Us, use_lds);
-    }
-    if (active) {
-        for (int64_t i = slot; i < cnt; i += slots) {
+    const Frame f(Us);
+    const NodeRows<VW> in(s_in, W, f);
+    const Rows<kNodeRows, VW, u64> dst(s_out, W, f);
+    UnitCount<VW, COUNT, NK> uc(f, lds_cnt, counts, use_lds);
+    if (f.active) {
+        for (int64_t i = f.slot; i < cnt; i += f.slots) {
             u64 out[VW];
-            cls_node<D, VW>(order, cell, i, dd, W, s_in, s_out, unit, out);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << NK) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, unit0);
-            }
+            cls_node<D, VW>(order, cell, i, dd, in, dst, out);
+            uc.add(f, out);
         }
     }
-    count_epilogue<VW, COUNT, kBlock, NK>(vc, active, unit, unit0, Us, lds_cnt, use_lds, counts);
+    uc.finish(f);
 }
 
 // The counting sweep of a rollout over the degree classes D <= 8 in one
@@ -1062,38 +946,34 @@ __global__ void __launch_bounds__(kBlock) k_sweep_cls_all_rp(const int32_t* __re
                                                              unsigned long long* __restrict__ counts, int use_lds,
                                                              int64_t Us) {
     extern __shared__ unsigned lds_cnt[];
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = t % Us, slot = t / Us;
-    const bool active = slot < slots;
-    VertCounter<VW, kClsAllPlanes> vc;
-    vc.reset();
-    lds_count_init<VW>(lds_cnt, Us, use_lds);
-    if (active) {
+    const Frame f(Us);
+    const NodeRows<VW> in(s_in, W, f);
+    const Rows<kNodeRows, VW, u64> dst(s_out, W, f);
+    UnitCount<VW, true, kClsAllPlanes> uc(f, lds_cnt, counts, use_lds);
+    if (f.active) {
         int c = 0;
-        for (int64_t i = tab.i0[0] + slot; i < tab.i0[tab.nc]; i += slots) {
+        for (int64_t i = tab.i0[0] + f.slot; i < tab.i0[tab.nc]; i += f.slots) {
             while (i >= tab.i0[c + 1]) ++c;
             const int32_t* o = order + tab.i0[c];
             const int32_t* cl = cell + tab.base[c];
             const int64_t r = i - tab.i0[c];
             u64 out[VW];
             switch (tab.D[c]) {
-                case 0: cls_node<0, VW>(o, cl, r, 0, W, s_in, s_out, unit, out); break;
-                case 1: cls_node<1, VW>(o, cl, r, 1, W, s_in, s_out, unit, out); break;
-                case 2: cls_node<2, VW>(o, cl, r, 2, W, s_in, s_out, unit, out); break;
-                case 3: cls_node<3, VW>(o, cl, r, 3, W, s_in, s_out, unit, out); break;
-                case 4: cls_node<4, VW>(o, cl, r, 4, W, s_in, s_out, unit, out); break;
-                case 5: cls_node<5, VW>(o, cl, r, 5, W, s_in, s_out, unit, out); break;
-                case 6: cls_node<6, VW>(o, cl, r, 6, W, s_in, s_out, unit, out); break;
-                case 7: cls_node<7, VW>(o, cl, r, 7, W, s_in, s_out, unit, out); break;
-                case 8: cls_node<8, VW>(o, cl, r, 8, W, s_in, s_out, unit, out); break;
+                case 0: cls_node<0, VW>(o, cl, r, 0, in, dst, out); break;
+                case 1: cls_node<1, VW>(o, cl, r, 1, in, dst, out); break;
+                case 2: cls_node<2, VW>(o, cl, r, 2, in, dst, out); break;
+                case 3: cls_node<3, VW>(o, cl, r, 3, in, dst, out); break;
+                case 4: cls_node<4, VW>(o, cl, r, 4, in, dst, out); break;
+                case 5: cls_node<5, VW>(o, cl, r, 5, in, dst, out); break;
+                case 6: cls_node<6, VW>(o, cl, r, 6, in, dst, out); break;
+                case 7: cls_node<7, VW>(o, cl, r, 7, in, dst, out); break;
+                case 8: cls_node<8, VW>(o, cl, r, 8, in, dst, out); break;
                 default: __builtin_unreachable();        // the host passes D <= 8 only
             }
-            vc.add(out);
-            if (vc.added == (1 << kClsAllPlanes) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, 0);
+            uc.add(f, out);
         }
     }
-    count_epilogue<VW, true, kBlock, kClsAllPlanes>(vc, active, unit, 0, Us, lds_cnt, use_lds, counts);
+    uc.finish(f);
 }
 
 // The classes above D = 8 (few nodes each: Poisson tail) in one launch: a
@@ -1116,56 +996,23 @@ __global__ void __launch_bounds__(kBlock) k_sweep_cls_gen_rp(const int32_t* __re
                                                              unsigned long long* __restrict__ counts, int use_lds,
                                                              int64_t Us) {
     extern __shared__ unsigned lds_cnt[];
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = t % Us, slot = t / Us;
-    const bool active = slot < slots;
-    VertCounter<VW> vc;
-    if constexpr (COUNT) {
-        vc.reset();
-        lds_count_init<VW>(lds_cnt, Us, use_lds);
-    }
-    if (active) {
+    const Frame f(Us);
+    const NodeRows<VW> in(s_in, W, f);
+    const Rows<kNodeRows, VW, u64> dst(s_out, W, f);
+    UnitCount<VW, COUNT> uc(f, lds_cnt, counts, use_lds);
+    if (f.active) {
         int c = 0;
-        for (int64_t i = slot; i < tab.i0[tab.nc]; i += slots) {
+        for (int64_t i = f.slot; i < tab.i0[tab.nc]; i += f.slots) {
             while (i >= tab.i0[c + 1]) ++c;
             const int dd = tab.D[c];
-            const int32_t* row = cell + tab.base[c] + (i - tab.i0[c]) * dd;
             const int64_t v = order[i];
-            BitCounter<8> bc[VW];
-#pragma unroll
-            for (int q = 0; q < VW; ++q) bc[q].reset();
-            int j = 0;
-            for (; j + 4 <= dd; j += 4) {
-                int32_t k[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) k[m] = row[j + m];
-                u64 x[4][VW];
-#pragma unroll
-                for (int m = 0; m < 4; ++m) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int q = 0; q < VW; ++q) bc[q].add(x[m][q]);
-            }
-            for (; j < dd; ++j) {
-                u64 x[VW];
-                ldv<VW>(s_in + (int64_t)row[j] * W + unit * VW, x);
-#pragma unroll
-                for (int q = 0; q < VW; ++q) bc[q].add(x[q]);
-            }
             u64 own[VW], out[VW];
-            ldv<VW>(s_in + v * W + unit * VW, own);
-#pragma unroll
-            for (int q = 0; q < VW; ++q) out[q] = bc[q].majority(dd, own[q]);
-            stv<VW>(s_out + v * W + unit * VW, out);
-            if constexpr (COUNT) {
-                vc.add(out);
-                if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, 0);
-            }
+            row_node<VW>(cell + tab.base[c] + (i - tab.i0[c]) * dd, dd, v, in, own, out);
+            stv<VW>(dst(v), out);
+            uc.add(f, out);
         }
     }
-    count_epilogue<VW, COUNT>(vc, active, unit, 0, Us, lds_cnt, use_lds, counts);
+    uc.finish(f);
 }
 
 // Gather floor of the degree-class sweep (bench `er.floor_ms`, VERDICT r05
@@ -1180,18 +1027,18 @@ __global__ void __launch_bounds__(kBlock) k_gather_floor_cls(const int32_t* __re
                                                              const int32_t* __restrict__ cell, GenTable tab,
                                                              int64_t W, const u64* __restrict__ s_in,
                                                              u64* __restrict__ s_out, int64_t Us) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / Us;
-    const int64_t unit = t % Us, slot = t / Us;
-    if (slot >= slots) return;
+    const Frame f(Us);
+    const NodeRows<VW> in(s_in, W, f);
+    const Rows<kNodeRows, VW, u64> dst(s_out, W, f);
+    if (!f.active) return;
     int c = 0;
-    for (int64_t i = slot; i < tab.i0[tab.nc]; i += slots) {
+    for (int64_t i = f.slot; i < tab.i0[tab.nc]; i += f.slots) {
         while (i >= tab.i0[c + 1]) ++c;
         const int dd = tab.D[c];
         const int32_t* row = cell + tab.base[c] + (i - tab.i0[c]) * dd;
         const int64_t v = order[i];
         u64 acc[VW];
-        if (dd % 2 == 0) ldv<VW>(s_in + v * W + unit * VW, acc);
+        if (dd % 2 == 0) ldv<VW>(in(v), acc);
         else {
 #pragma unroll
             for (int q = 0; q < VW; ++q) acc[q] = 0;
@@ -1203,14 +1050,14 @@ __global__ void __launch_bounds__(kBlock) k_gather_floor_cls(const int32_t* __re
             u64 x[8][VW];
 #pragma unroll
             for (int m = 0; m < 8; ++m)
-                if (k[m] >= 0) ldv<VW>(s_in + (int64_t)k[m] * W + unit * VW, x[m]);
+                if (k[m] >= 0) ldv<VW>(in((int64_t)k[m]), x[m]);
 #pragma unroll
             for (int m = 0; m < 8; ++m)
                 if (k[m] >= 0)
 #pragma unroll
                     for (int q = 0; q < VW; ++q) acc[q] ^= x[m][q];
         }
-        stv<VW>(s_out + v * W + unit * VW, acc);
+        stv<VW>(dst(v), acc);
     }
 }
 
@@ -1253,23 +1100,16 @@ template <int VW>
 __global__ void __launch_bounds__(kBlock) k_popcount_rp(const u64* __restrict__ bits, int64_t n, int64_t W,
                                                         unsigned long long* __restrict__ counts, int use_lds) {
     extern __shared__ unsigned lds_cnt[];
-    const int64_t U = W / VW;
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t slots = ((int64_t)gridDim.x * kBlock) / U;
-    const int64_t unit = t % U, slot = t / U;
-    const bool active = slot < slots;
-    VertCounter<VW> vc;
-    vc.reset();
-    lds_count_init<VW>(lds_cnt, U, use_lds);
-    if (active) {
-        for (int64_t v = slot; v < n; v += slots) {
+    const Frame f(W / VW);
+    UnitCount<VW, true> uc(f, lds_cnt, counts, use_lds);
+    if (f.active) {
+        for (int64_t v = f.slot; v < n; v += f.slots) {
             u64 x[VW];
-            ldv<VW>(bits + v * W + unit * VW, x);
-            vc.add(x);
-            if (vc.added == (1 << KC) - 1) flush_to(vc, use_lds, lds_cnt, counts, unit, 0);
+            ldv<VW>(bits + v * W + f.unit * VW, x);
+            uc.add(f, x);
         }
     }
-    count_epilogue<VW, true>(vc, active, unit, 0, U, lds_cnt, use_lds, counts);
+    uc.finish(f);
 }
 
 }  // namespace mjx
@@ -1388,39 +1228,33 @@ static int launch_sweep_csr_np(const int64_t* rp, const int32_t* col, int64_t n,
     return MJX_OK;
 }
 
-constexpr int kCountBlock = kBlock;
-
-template <int VW, bool COUNT, int IK = kNodeRows, int OK = kNodeRows>
-static void launch_ell_rp_vw(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
-                             unsigned long long* counts, int grid, size_t lds, int use_lds, int64_t unit0,
-                             int64_t Us, const SliceGeom& sg, hipStream_t st) {
-    constexpr int BS = COUNT ? kCountBlock : kBlock;
-    (void)grid;
-    auto ell = [&](auto kern) {
-        const int g = resident_grid(kern, BS, lds, n * Us);
-        kern<<<g, BS, lds, st>>>(adj, n, W, in, out, counts, use_lds, unit0, Us, GeomArg<(IK | OK) != 0>(sg));
-    };
-    switch (d) {
-        case 3: ell(k_sweep_ell_rp<3, VW, COUNT, BS, IK, OK>); break;
-        case 4: ell(k_sweep_ell_rp<4, VW, COUNT, BS, IK, OK>); break;
-        case 6: ell(k_sweep_ell_rp<6, VW, COUNT, BS, IK, OK>); break;
-        default: {
-            auto kern = k_sweep_gen_rp<VW, COUNT, false, IK, OK>;
-            const int g = resident_grid(kern, kBlock, lds, n * Us);
-            kern<<<g, kBlock, lds, st>>>(adj, d, nullptr, nullptr, nullptr, n, W, in, out, counts, use_lds, unit0, Us,
-                                         GeomArg<(IK | OK) != 0>(sg));
-            break;
-        }
-    }
+// The runtime unit width (vw = 1 or 2 words) and "counting" of a launch as
+// compile-time constants: f(integral_constant<int, VW>{}[, bool_constant<COUNT>{}]).
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F>
+static void with_vw(int vw, F&& f) {
+    if (vw == 2) f(int_c<2>{}); else f(int_c<1>{});
+}
+template <typename F>
+static void with_vw_count(int vw, bool counting, F&& f) {
+    with_vw(vw, [&](auto VW) {
+        if (counting) f(VW, std::true_type{}); else f(VW, std::false_type{});
+    });
 }
 
-// Geometry of one launch over Us units (of VW words) of every node.
-static int rp_geometry(int64_t n, int64_t W, int64_t Us, int* grid, int* vw, int* use_lds, size_t* lds) {
+// One launch of `kern` over `work` threads' worth of items on a grid of what
+// is resident at once (resident_grid), `lds` bytes of dynamic LDS.
+template <typename K, typename... A>
+static void launch(K* kern, size_t lds, int64_t work, hipStream_t st, const A&... args) {
+    kern<<<resident_grid(kern, kBlock, lds, work), kBlock, lds, st>>>(args...);
+}
+
+// Geometry of one launch over Us units (of vw words) of every node; the fused
+// counters sit in LDS (use_lds, lds bytes) when counting and they fit.
+static int rp_geometry(int64_t n, int64_t W, int64_t Us, bool counting, int* vw, int* use_lds, size_t* lds) {
     *vw = (W % 2 == 0) ? 2 : 1;
-    *grid = grid_for(n * Us);
-    const int64_t threads = (int64_t)(*grid) * kBlock;
-    if (threads / Us < 1) return MJX_ERANGE;
-    *use_lds = (Us * (*vw) * 64 <= kMaxLdsReplicas) ? 1 : 0;
+    if ((int64_t)grid_for(n * Us) * kBlock / Us < 1) return MJX_ERANGE;
+    *use_lds = (counting && Us * (*vw) * 64 <= kMaxLdsReplicas) ? 1 : 0;
     *lds = *use_lds ? (size_t)(Us * (*vw) * 64 * sizeof(unsigned)) : 0;
     return MJX_OK;
 }
@@ -1430,6 +1264,28 @@ static int rp_geometry(int64_t n, int64_t W, int64_t Us, int* grid, int* vw, int
 // slice (what that is worth: the plan below, mjx_rollout_ell_rp_plan).
 static int64_t units_of(int64_t W) { return (W % 2 == 0) ? W / 2 : W; }
 
+// One ELL sweep (plain, or tracked: ta) by degree: the specialised kernels, else runtime-degree rows.
+template <int VW, bool COUNT, int IK, int OK, bool TRACK = false>
+static void launch_ell_rp(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
+                          unsigned long long* counts, size_t lds, int use_lds, int64_t unit0, int64_t Us,
+                          const SliceGeom& sg, hipStream_t st, const TrackArg<TRACK>& ta = {}) {
+    const GeomArg<(IK | OK) != 0> ga(sg);
+    auto ell = [&](auto kern) {
+        launch(kern, lds, n * Us, st, adj, n, W, in, out, counts, use_lds, unit0, Us, ga, ta);
+    };
+    switch (d) {
+        case 3: ell(k_sweep_ell_rp<3, VW, COUNT, IK, OK, TRACK>); break;
+        case 4: ell(k_sweep_ell_rp<4, VW, COUNT, IK, OK, TRACK>); break;
+        case 6: ell(k_sweep_ell_rp<6, VW, COUNT, IK, OK, TRACK>); break;
+        default:
+            launch(k_sweep_gen_rp<VW, COUNT, false, IK, OK, TRACK>, lds, n * Us, st, adj, d, nullptr, nullptr, nullptr,
+                   n, W, in, out, counts, use_lds, unit0, Us, ga, ta);
+            break;
+    }
+}
+
+constexpr SliceGeom kNoSlices{0, 1, 0, 1};
+
 // One sweep over the units [unit0, unit0 + Us) of every node, `in` read through
 // a view of kind ik and `out` written through one of kind ok (RowKind; sg holds
 // the slice-major geometry, unused by node-major views).  The count rides only
@@ -1437,60 +1293,36 @@ static int64_t units_of(int64_t W) { return (W % 2 == 0) ? W / 2 : W; }
 static int launch_sweep_ell_rp_v(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, int ik, u64* out,
                                  int ok, const SliceGeom& sg, unsigned long long* counts, int64_t unit0,
                                  int64_t Us, hipStream_t st) {
-    int grid, vw, use_lds; size_t lds;
-    int rc = rp_geometry(n, W, Us, &grid, &vw, &use_lds, &lds);
+    int vw, use_lds; size_t lds;
+    int rc = rp_geometry(n, W, Us, counts != nullptr, &vw, &use_lds, &lds);
     if (rc) return rc;
-    if (!counts) { lds = 0; use_lds = 0; }
     if (counts && ok != kNodeRows) return MJX_EINVAL;
-#define MJX_ELL(VWV, C, IKV, OKV) \
-    launch_ell_rp_vw<VWV, C, IKV, OKV>(adj, n, d, W, in, out, counts, grid, lds, use_lds, unit0, Us, sg, st)
-#define MJX_ELL_VIEWS(VWV)                                                           \
-    do {                                                                             \
-        if (ik == kNodeRows && ok == kNodeRows) {                                    \
-            if (counts) MJX_ELL(VWV, true, kNodeRows, kNodeRows);                    \
-            else MJX_ELL(VWV, false, kNodeRows, kNodeRows);                          \
-        } else if (ik == kNodeRows) {                                                \
-            MJX_ELL(VWV, false, kNodeRows, kSliceRows);                              \
-        } else if (ok == kSliceRows) {                                               \
-            MJX_ELL(VWV, false, kSliceRows, kSliceRows);                             \
-        } else {                                                                     \
-            if (counts) MJX_ELL(VWV, true, kSliceRows, kNodeRows);                   \
-            else MJX_ELL(VWV, false, kSliceRows, kNodeRows);                         \
-        }                                                                            \
-    } while (0)
-    if (vw == 2) MJX_ELL_VIEWS(2); else MJX_ELL_VIEWS(1);
-#undef MJX_ELL_VIEWS
-#undef MJX_ELL
+    with_vw_count(vw, counts != nullptr, [&](auto VW, auto COUNT) {
+        auto go = [&](auto IK, auto OK) {
+            // counts with a slice-major output was refused above: that combination is not instantiated
+            if constexpr (!COUNT || OK == kNodeRows)
+                launch_ell_rp<VW, COUNT, IK, OK>(adj, n, d, W, in, out, counts, lds, use_lds, unit0, Us, sg, st);
+        };
+        const int_c<kNodeRows> node;
+        const int_c<kSliceRows> slice;
+        if (ik == kNodeRows && ok == kNodeRows) go(node, node);
+        else if (ik == kNodeRows) go(node, slice);
+        else if (ok == kSliceRows) go(slice, slice);
+        else go(slice, node);
+    });
     MJX_LAUNCH_CHECK("sweep_ell_rp");
     return MJX_OK;
 }
 
-static int launch_sweep_ell_rp(const int32_t* adj, int64_t n, int d, int64_t W, const u64* in, u64* out,
-                               unsigned long long* counts, int64_t unit0, int64_t Us, hipStream_t st) {
-    return launch_sweep_ell_rp_v(adj, n, d, W, in, kNodeRows, out, kNodeRows, SliceGeom{0, 1, 0, 1}, counts, unit0, Us,
-                                 st);
-}
-
 static int launch_sweep_csr_rp(const int64_t* rp, const int32_t* col, const int32_t* order, int64_t n, int64_t W,
-                               const u64* in, u64* out, unsigned long long* counts, int64_t unit0, int64_t Us,
-                               hipStream_t st) {
-    int grid, vw, use_lds; size_t lds;
-    int rc = rp_geometry(n, W, Us, &grid, &vw, &use_lds, &lds);
+                               const u64* in, u64* out, unsigned long long* counts, int64_t Us, hipStream_t st) {
+    int vw, use_lds; size_t lds;
+    int rc = rp_geometry(n, W, Us, counts != nullptr, &vw, &use_lds, &lds);
     if (rc) return rc;
-    if (!counts) { lds = 0; use_lds = 0; }
-#define MJX_CSR(VWV, C)                                                                                      \
-    do {                                                                                                     \
-        auto kern = k_sweep_gen_rp<VWV, C, true>;                                                            \
-        grid = resident_grid(kern, kBlock, lds, n * Us);                                                     \
-        kern<<<grid, kBlock, lds, st>>>(nullptr, 0, rp, col, order, n, W, in, out, counts, use_lds, unit0, Us, \
-                                        GeomArg<false>(SliceGeom{0, 1, 0, 1}));                              \
-    } while (0)
-    if (vw == 2) {
-        if (counts) MJX_CSR(2, true); else MJX_CSR(2, false);
-    } else {
-        if (counts) MJX_CSR(1, true); else MJX_CSR(1, false);
-    }
-#undef MJX_CSR
+    with_vw_count(vw, counts != nullptr, [&](auto VW, auto COUNT) {
+        launch(k_sweep_gen_rp<VW, COUNT, true>, lds, n * Us, st, nullptr, 0, rp, col, order, n, W, in, out,
+               counts, use_lds, (int64_t)0, Us, GeomArg<false>(kNoSlices), TrackArg<false>{});
+    });
     MJX_LAUNCH_CHECK("sweep_csr_rp");
     return MJX_OK;
 }
@@ -1524,34 +1356,51 @@ extern "C" int mjx_popcount_rp(const uint64_t* bits, int64_t n, int64_t words, u
                                void* stream) {
     if (n < 0 || words < 1 || !counts || (n > 0 && !bits)) return MJX_EINVAL;
     if (n == 0) return MJX_OK;
-    int grid, vw, use_lds; size_t lds;
-    int rc = rp_geometry(n, words, units_of(words), &grid, &vw, &use_lds, &lds);
+    int vw, use_lds; size_t lds;
+    int rc = rp_geometry(n, words, units_of(words), true, &vw, &use_lds, &lds);
     if (rc) return rc;
-    hipStream_t st = as_stream(stream);
-    if (vw == 2) k_popcount_rp<2><<<grid, kBlock, lds, st>>>((const u64*)bits, n, words, counts, use_lds);
-    else k_popcount_rp<1><<<grid, kBlock, lds, st>>>((const u64*)bits, n, words, counts, use_lds);
+    const int grid = grid_for(n * units_of(words));
+    with_vw(vw, [&](auto VW) {
+        k_popcount_rp<VW><<<grid, kBlock, lds, as_stream(stream)>>>((const u64*)bits, n, words, counts, use_lds);
+    });
     MJX_LAUNCH_CHECK("mjx_popcount_rp");
     return MJX_OK;
 }
 
 static bool overlaps(const void* a, const void* b) { return a && b && a == b; }
 
-extern "C" int mjx_rollout_ell_np(const int32_t* adj, int64_t n, int d, const uint64_t* s_in, uint64_t* s_out,
-                                  uint64_t* tmp, int steps, unsigned long long* counts, void* stream) {
-    if (n < 0 || d < 0 || d > 255 || (n > 0 && (!adj && d > 0)) || (n > 0 && (!s_in || !s_out))) return MJX_EINVAL;
+// The argument checks every rollout starts with, in this order: `bad` (the
+// entry point's own conditions) or a bad size or state pointer, n beyond int32
+// node indices, aliased state buffers.  The callers go on with "n == 0: done",
+// "steps < 0: invalid" and rollout_copy for steps == 0, in the order each has.
+static int check_rollout(bool bad, int64_t n, const void* s_in, const void* s_out, const void* tmp) {
+    if (bad || n < 0 || (n > 0 && (!s_in || !s_out))) return MJX_EINVAL;
     if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
     if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
+    return MJX_OK;
+}
+
+// A rollout of no steps: s_out = s_in and its +1 counts; `words` words a node
+// (replica-packed), or words == 0: the node-packed layout.
+static int rollout_copy(int64_t n, int64_t words, const uint64_t* s_in, uint64_t* s_out, unsigned long long* counts,
+                        void* stream) {
+    const size_t bytes = words ? (size_t)n * (size_t)words * 8 : (size_t)((n + 63) / 64) * 8;
+    MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, as_stream(stream)), "rollout copy");
+    if (!counts) return MJX_OK;
+    return words ? mjx_popcount_rp(s_out, n, words, counts, stream) : mjx_popcount_np(s_out, n, counts, stream);
+}
+
+extern "C" int mjx_rollout_ell_np(const int32_t* adj, int64_t n, int d, const uint64_t* s_in, uint64_t* s_out,
+                                  uint64_t* tmp, int steps, unsigned long long* counts, void* stream) {
+    int rc = check_rollout(d < 0 || d > 255 || (n > 0 && !adj && d > 0), n, s_in, s_out, tmp);
+    if (rc) return rc;
     if (n == 0) return MJX_OK;
+    if (steps < 0) return MJX_EINVAL;
+    if (steps == 0) return rollout_copy(n, 0, s_in, s_out, counts, stream);
     hipStream_t st = as_stream(stream);
-    const size_t bytes = (size_t)((n + 63) / 64) * 8;
     auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {
         return launch_sweep_ell_np(adj, 0, n, d, a, b, c, st);
     };
-    if (steps < 0) return MJX_EINVAL;
-    if (steps == 0) {
-        MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, st), "rollout copy");
-        return counts ? mjx_popcount_np(s_out, n, counts, stream) : MJX_OK;
-    }
     return run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
 }
 
@@ -1605,12 +1454,10 @@ extern "C" int mjx_rollout_ell_rp_plan(int64_t n, int d, int64_t words, int step
 
 static int check_rollout_ell_rp(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
                                 uint64_t* s_out, uint64_t* tmp, int steps, int slices) {
-    if (n < 0 || d < 0 || d > 255 || words < 1 || slices < 0 || (n > 0 && (!s_in || !s_out || (!adj && d > 0))))
-        return MJX_EINVAL;
-    if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
-    if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
-    if (steps < 0) return MJX_EINVAL;
-    return MJX_OK;
+    int rc = check_rollout(d < 0 || d > 255 || words < 1 || slices < 0 || (n > 0 && !adj && d > 0), n, s_in, s_out,
+                           tmp);
+    if (rc) return rc;
+    return steps < 0 ? MJX_EINVAL : MJX_OK;      // before "n == 0: done" here
 }
 
 extern "C" int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, int64_t words, const uint64_t* s_in,
@@ -1619,12 +1466,8 @@ extern "C" int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, i
     int rc = check_rollout_ell_rp(adj, n, d, words, s_in, s_out, tmp, steps, slices);
     if (rc) return rc;
     if (n == 0) return MJX_OK;
+    if (steps == 0) return rollout_copy(n, words, s_in, s_out, counts, stream);
     hipStream_t st = as_stream(stream);
-    const size_t bytes = (size_t)n * (size_t)words * 8;
-    if (steps == 0) {
-        MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, st), "rollout copy");
-        return counts ? mjx_popcount_rp(s_out, n, words, counts, stream) : MJX_OK;
-    }
     const int64_t U = units_of(words);
     int S = slices;
     if (!S) {
@@ -1637,7 +1480,7 @@ extern "C" int mjx_rollout_ell_rp_sliced(const int32_t* adj, int64_t n, int d, i
     const int64_t Us = U / S;
     for (int q = 0; q < S; ++q) {
         auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {
-            return launch_sweep_ell_rp(adj, n, d, words, a, b, c, q * Us, Us, st);
+            return launch_sweep_ell_rp_v(adj, n, d, words, a, kNodeRows, b, kNodeRows, kNoSlices, c, q * Us, Us, st);
         };
         rc = run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
         if (rc) return rc;
@@ -1773,17 +1616,12 @@ extern "C" int mjx_rollout_ell_rp(const int32_t* adj, int64_t n, int d, int64_t 
 extern "C" int mjx_rollout_csr_np(const int64_t* row_ptr, const int32_t* col, int64_t n, const uint64_t* s_in,
                                   uint64_t* s_out, uint64_t* tmp, int steps, unsigned long long* counts,
                                   void* stream) {
-    if (n < 0 || (n > 0 && (!row_ptr || !s_in || !s_out))) return MJX_EINVAL;
-    if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
-    if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
+    int rc = check_rollout(n > 0 && !row_ptr, n, s_in, s_out, tmp);
+    if (rc) return rc;
     if (n == 0) return MJX_OK;
-    hipStream_t st = as_stream(stream);
-    const size_t bytes = (size_t)((n + 63) / 64) * 8;
     if (steps < 0) return MJX_EINVAL;
-    if (steps == 0) {
-        MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, st), "rollout copy");
-        return counts ? mjx_popcount_np(s_out, n, counts, stream) : MJX_OK;
-    }
+    if (steps == 0) return rollout_copy(n, 0, s_in, s_out, counts, stream);
+    hipStream_t st = as_stream(stream);
     auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {
         return launch_sweep_csr_np(row_ptr, col, n, a, b, c, st);
     };
@@ -1793,28 +1631,16 @@ extern "C" int mjx_rollout_csr_np(const int64_t* row_ptr, const int32_t* col, in
 extern "C" int mjx_rollout_csr_rp_ordered(const int64_t* row_ptr, const int32_t* col, const int32_t* order,
                                           int64_t n, int64_t words, const uint64_t* s_in, uint64_t* s_out,
                                           uint64_t* tmp, int steps, unsigned long long* counts, void* stream) {
-    if (n < 0 || words < 1 || (n > 0 && (!row_ptr || !s_in || !s_out))) return MJX_EINVAL;
-    if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
-    if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
+    int rc = check_rollout(words < 1 || (n > 0 && !row_ptr), n, s_in, s_out, tmp);
+    if (rc) return rc;
     if (n == 0) return MJX_OK;
-    hipStream_t st = as_stream(stream);
-    const size_t bytes = (size_t)n * (size_t)words * 8;
     if (steps < 0) return MJX_EINVAL;
-    if (steps == 0) {
-        MJX_HIP(hipMemcpyAsync(s_out, s_in, bytes, hipMemcpyDeviceToDevice, st), "rollout copy");
-        return counts ? mjx_popcount_rp(s_out, n, words, counts, stream) : MJX_OK;
-    }
-    const int64_t U = units_of(words);
-    const int S = 1;                                   // the CSR rollout is not sliced
-    const int64_t Us = U / S;
-    for (int q = 0; q < S; ++q) {
-        auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {
-            return launch_sweep_csr_rp(row_ptr, col, order, n, words, a, b, c, q * Us, Us, st);
-        };
-        int rc = run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
-        if (rc) return rc;
-    }
-    return MJX_OK;
+    if (steps == 0) return rollout_copy(n, words, s_in, s_out, counts, stream);
+    hipStream_t st = as_stream(stream);
+    auto sweep = [&](const u64* a, u64* b, unsigned long long* c) {     // one slice: the CSR rollout is not sliced
+        return launch_sweep_csr_rp(row_ptr, col, order, n, words, a, b, c, units_of(words), st);
+    };
+    return run_rollout(steps, (const u64*)s_in, (u64*)s_out, (u64*)tmp, counts, sweep);
 }
 
 // ---- degree-class ELL ------------------------------------------------------
@@ -1855,66 +1681,46 @@ static int64_t cls_count_threads(int64_t cnt, int64_t Us) {
     return (slots < 1 ? 1 : slots) * Us;
 }
 
+// One class of degree D <= 8, its own kernel each.
 template <int VW, bool COUNT>
-static int launch_sweep_cls_gen_rp(const int32_t* order, const int32_t* cell, const GenTable& tab, int64_t W,
-                                   const u64* in, u64* out, unsigned long long* counts, size_t lds, int use_lds,
-                                   int64_t Us, hipStream_t st) {
-    auto kern = k_sweep_cls_gen_rp<VW, COUNT>;
-    const int64_t cnt = tab.i0[tab.nc];
-    const int g = resident_grid(kern, kBlock, lds, COUNT ? cls_count_threads(cnt, Us) : cnt * Us);
-    kern<<<g, kBlock, lds, st>>>(order, cell, tab, W, in, out, counts, use_lds, Us);
-    MJX_LAUNCH_CHECK("sweep_cls_gen_rp");
-    return MJX_OK;
-}
-
-template <int VW, bool COUNT>
-static int launch_sweep_cls_rp(const int32_t* order, const int32_t* cell, int64_t cnt, int D, int64_t W,
-                               const u64* in, u64* out, unsigned long long* counts, size_t lds, int use_lds,
-                               int64_t unit0, int64_t Us, hipStream_t st) {
+static void launch_sweep_cls_rp(const int32_t* order, const int32_t* cell, int64_t cnt, int D, int64_t W,
+                                const u64* in, u64* out, unsigned long long* counts, size_t lds, int use_lds,
+                                int64_t Us, hipStream_t st) {
     auto go = [&](auto kern) {
-        const int g = resident_grid(kern, kBlock, lds, COUNT ? cls_count_threads(cnt, Us) : cnt * Us);
-        kern<<<g, kBlock, lds, st>>>(order, cell, cnt, D, W, in, out, counts, use_lds, unit0, Us);
+        launch(kern, lds, COUNT ? cls_count_threads(cnt, Us) : cnt * Us, st, order, cell, cnt, D, W, in, out, counts,
+               use_lds, Us);
     };
-#define MJX_CLS(DD) go(k_sweep_cls_rp<DD, VW, COUNT>)
     switch (D) {
-        case 0: MJX_CLS(0); break;
-        case 1: MJX_CLS(1); break;
-        case 2: MJX_CLS(2); break;
-        case 3: MJX_CLS(3); break;
-        case 4: MJX_CLS(4); break;
-        case 5: MJX_CLS(5); break;
-        case 6: MJX_CLS(6); break;
-        case 7: MJX_CLS(7); break;
-        case 8: MJX_CLS(8); break;
-        default: MJX_CLS(-1); break;
+        case 0: go(k_sweep_cls_rp<0, VW, COUNT>); break;
+        case 1: go(k_sweep_cls_rp<1, VW, COUNT>); break;
+        case 2: go(k_sweep_cls_rp<2, VW, COUNT>); break;
+        case 3: go(k_sweep_cls_rp<3, VW, COUNT>); break;
+        case 4: go(k_sweep_cls_rp<4, VW, COUNT>); break;
+        case 5: go(k_sweep_cls_rp<5, VW, COUNT>); break;
+        case 6: go(k_sweep_cls_rp<6, VW, COUNT>); break;
+        case 7: go(k_sweep_cls_rp<7, VW, COUNT>); break;
+        case 8: go(k_sweep_cls_rp<8, VW, COUNT>); break;
+        default: go(k_sweep_cls_rp<-1, VW, COUNT>); break;
     }
-#undef MJX_CLS
-    MJX_LAUNCH_CHECK("sweep_cls_rp");
-    return MJX_OK;
 }
 
 extern "C" int mjx_rollout_class_rp(const int32_t* order, const int32_t* cell, const int64_t* classes,
                                     int nclasses, int64_t n, int64_t words, const uint64_t* s_in,
                                     uint64_t* s_out, uint64_t* tmp, int steps, unsigned long long* counts,
                                     void* stream) {
-    if (n < 0 || words < 1 || (n > 0 && (!order || !s_in || !s_out))) return MJX_EINVAL;
-    if (n > (int64_t)INT32_MAX) return MJX_ERANGE;
-    if (overlaps(s_in, s_out) || overlaps(s_in, tmp) || overlaps(s_out, tmp)) return MJX_EINVAL;
-    int rc = check_classes(classes, nclasses, n);
+    int rc = check_rollout(words < 1 || (n > 0 && !order), n, s_in, s_out, tmp);
+    if (rc) return rc;
+    rc = check_classes(classes, nclasses, n);
     if (rc) return rc;
     if (n == 0) return MJX_OK;
     for (int c = 0; c < nclasses; ++c)
         if (classes[4 * c + 1] * classes[4 * c + 2] > 0 && !cell) return MJX_EINVAL;
-    hipStream_t st = as_stream(stream);
     if (steps < 0) return MJX_EINVAL;
-    if (steps == 0) {
-        MJX_HIP(hipMemcpyAsync(s_out, s_in, (size_t)n * (size_t)words * 8, hipMemcpyDeviceToDevice, st),
-                "rollout copy");
-        return counts ? mjx_popcount_rp(s_out, n, words, counts, stream) : MJX_OK;
-    }
+    if (steps == 0) return rollout_copy(n, words, s_in, s_out, counts, stream);
+    hipStream_t st = as_stream(stream);
     const int64_t Us = units_of(words);
-    int grid, vw, use_lds; size_t lds;
-    rc = rp_geometry(n, words, Us, &grid, &vw, &use_lds, &lds);
+    int vw, cnt_use_lds; size_t cnt_lds;         // of a counting sweep; a plain one uses no LDS
+    rc = rp_geometry(n, words, Us, true, &vw, &cnt_use_lds, &cnt_lds);
     if (rc) return rc;
     // the counting sweep of the leading classes with D <= 8 that tile `order`
     // from position 0 in one launch (-DMJX_CLS_PER_LAUNCH: the per-class
@@ -1934,14 +1740,13 @@ extern "C" int mjx_rollout_class_rp(const int32_t* order, const int32_t* cell, c
     all.nc = lead;
     all.i0[lead] = lead ? all.i0[lead - 1] + classes[4 * (lead - 1) + 1] : 0;
     auto sweep = [&](const u64* a, u64* b, unsigned long long* cn) {
+        const size_t lds = cn ? cnt_lds : 0;
+        const int use_lds = cn ? cnt_use_lds : 0;
         const int c0 = (cn && lead >= 2) ? lead : 0;
         if (c0) {
-            auto go = [&](auto kern) {
-                const int g = resident_grid(kern, kBlock, lds, n * Us);
-                kern<<<g, kBlock, lds, st>>>(order, cell, all, words, a, b, cn, use_lds, Us);
-            };
-            if (vw == 2) go(k_sweep_cls_all_rp<2>);
-            else go(k_sweep_cls_all_rp<1>);
+            with_vw(vw, [&](auto VW) {
+                launch(k_sweep_cls_all_rp<VW>, lds, n * Us, st, order, cell, all, words, a, b, cn, use_lds, Us);
+            });
             MJX_LAUNCH_CHECK("sweep_cls_all_rp");
         }
         // runs of consecutive classes with D > 8 (adjacent in `order`) share one launch
@@ -1949,14 +1754,14 @@ extern "C" int mjx_rollout_class_rp(const int32_t* order, const int32_t* cell, c
         int64_t g0 = 0;
         auto flush_gen = [&]() -> int {
             if (tab.nc == 0) return MJX_OK;
-            const int32_t* o = order + g0;
-            int r;
-            if (vw == 2) r = cn ? launch_sweep_cls_gen_rp<2, true>(o, cell, tab, words, a, b, cn, lds, use_lds, Us, st)
-                                : launch_sweep_cls_gen_rp<2, false>(o, cell, tab, words, a, b, cn, 0, 0, Us, st);
-            else r = cn ? launch_sweep_cls_gen_rp<1, true>(o, cell, tab, words, a, b, cn, lds, use_lds, Us, st)
-                        : launch_sweep_cls_gen_rp<1, false>(o, cell, tab, words, a, b, cn, 0, 0, Us, st);
+            const int64_t cnt = tab.i0[tab.nc];
+            with_vw_count(vw, cn != nullptr, [&](auto VW, auto COUNT) {
+                launch(k_sweep_cls_gen_rp<VW, COUNT>, lds, COUNT ? cls_count_threads(cnt, Us) : cnt * Us, st,
+                       order + g0, cell, tab, words, a, b, cn, use_lds, Us);
+            });
+            MJX_LAUNCH_CHECK("sweep_cls_gen_rp");
             tab.nc = 0;
-            return r;
+            return MJX_OK;
         };
         for (int c = c0; c < nclasses; ++c) {
             const int64_t i0 = classes[4 * c], cnt = classes[4 * c + 1], base = classes[4 * c + 3];
@@ -1974,14 +1779,11 @@ extern "C" int mjx_rollout_class_rp(const int32_t* order, const int32_t* cell, c
                 ++tab.nc;
                 continue;
             }
-            const int32_t* o = order + i0;
-            const int32_t* cl = cell ? cell + base : nullptr;
-            int r;
-            if (vw == 2) r = cn ? launch_sweep_cls_rp<2, true>(o, cl, cnt, D, words, a, b, cn, lds, use_lds, 0, Us, st)
-                                : launch_sweep_cls_rp<2, false>(o, cl, cnt, D, words, a, b, cn, 0, 0, 0, Us, st);
-            else r = cn ? launch_sweep_cls_rp<1, true>(o, cl, cnt, D, words, a, b, cn, lds, use_lds, 0, Us, st)
-                        : launch_sweep_cls_rp<1, false>(o, cl, cnt, D, words, a, b, cn, 0, 0, 0, Us, st);
-            if (r) return r;
+            with_vw_count(vw, cn != nullptr, [&](auto VW, auto COUNT) {
+                launch_sweep_cls_rp<VW, COUNT>(order + i0, cell ? cell + base : nullptr, cnt, D, words, a, b, cn, lds,
+                                               use_lds, Us, st);
+            });
+            MJX_LAUNCH_CHECK("sweep_cls_rp");
         }
         return flush_gen();
     };
@@ -1998,8 +1800,8 @@ extern "C" int mjx_gather_floor_class(const int32_t* order, const int32_t* cell,
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
     const int64_t Us = units_of(words);
-    int grid, vw, use_lds; size_t lds;
-    rc = rp_geometry(n, words, Us, &grid, &vw, &use_lds, &lds);
+    int vw, use_lds; size_t lds;
+    rc = rp_geometry(n, words, Us, false, &vw, &use_lds, &lds);
     if (rc) return rc;
     // consecutive classes (adjacent in `order`), kMaxGen at a time
     for (int c0 = 0; c0 < nclasses;) {
@@ -2013,12 +1815,10 @@ extern "C" int mjx_gather_floor_class(const int32_t* order, const int32_t* cell,
             tab.i0[tab.nc + 1] = tab.i0[tab.nc] + classes[4 * c + 1];
             ++tab.nc;
         }
-        auto go = [&](auto kern) {
-            const int g = resident_grid(kern, kBlock, 0, tab.i0[tab.nc] * Us);
-            kern<<<g, kBlock, 0, st>>>(order + g0, cell, tab, words, (const u64*)s_in, (u64*)s_out, Us);
-        };
-        if (vw == 2) go(k_gather_floor_cls<2>);
-        else go(k_gather_floor_cls<1>);
+        with_vw(vw, [&](auto VW) {
+            launch(k_gather_floor_cls<VW>, 0, tab.i0[tab.nc] * Us, st, order + g0, cell, tab, words, (const u64*)s_in,
+                   (u64*)s_out, Us);
+        });
         MJX_LAUNCH_CHECK("gather_floor_cls");
         c0 = c;
     }
@@ -2039,10 +1839,8 @@ constexpr int64_t kMaxLdsDiffWords = 1024;   // 2 x 8 KiB of LDS flag words per 
 // rp_geometry, then the flag words.  Above kMaxLdsDiffWords words U >= 512 >
 // the block size, so the threads of a block own distinct units.
 static int track_geometry(int64_t n, int64_t W, bool counting, int* vw, int* use_lds, int* use_dlds, size_t* lds) {
-    int grid;
-    int rc = rp_geometry(n, W, units_of(W), &grid, vw, use_lds, lds);
+    int rc = rp_geometry(n, W, units_of(W), counting, vw, use_lds, lds);
     if (rc) return rc;
-    if (!counting) { *lds = 0; *use_lds = 0; }
     *use_dlds = (W <= kMaxLdsDiffWords) ? 1 : 0;
     if (*use_dlds) *lds += (size_t)(2 * W * sizeof(u64));
     return MJX_OK;
@@ -2068,32 +1866,11 @@ extern "C" int mjx_sweep_track_ell_rp(const int32_t* adj, int64_t n, int d, int6
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
     const int64_t U = units_of(words);
-    const u64* in = (const u64*)s_in;
-    const u64* prev = (const u64*)s_prev;
-    u64* out = (u64*)s_out;
-    u64* df = (u64*)diff;
-    auto ell = [&](auto kern) {
-        const int g = resident_grid(kern, kBlock, lds, n * U);
-        kern<<<g, kBlock, lds, st>>>(adj, n, words, in, prev, out, counts, use_lds, df, use_dlds, (int64_t)0, U);
-    };
-    auto gen = [&](auto kern) {
-        const int g = resident_grid(kern, kBlock, lds, n * U);
-        kern<<<g, kBlock, lds, st>>>(adj, d, nullptr, nullptr, nullptr, n, words, in, prev, out, counts, use_lds, df,
-                                     use_dlds, (int64_t)0, U);
-    };
-#define MJX_TRACK_ELL(VWV, C)                                             \
-    switch (d) {                                                          \
-        case 3: ell(k_sweep_track_ell_rp<3, VWV, C>); break;              \
-        case 4: ell(k_sweep_track_ell_rp<4, VWV, C>); break;              \
-        case 6: ell(k_sweep_track_ell_rp<6, VWV, C>); break;              \
-        default: gen(k_sweep_track_gen_rp<VWV, C, false>); break;         \
-    }
-    if (vw == 2) {
-        if (counts) { MJX_TRACK_ELL(2, true) } else { MJX_TRACK_ELL(2, false) }
-    } else {
-        if (counts) { MJX_TRACK_ELL(1, true) } else { MJX_TRACK_ELL(1, false) }
-    }
-#undef MJX_TRACK_ELL
+    const TrackArg<true> ta{(const u64*)s_prev, (u64*)diff, use_dlds};
+    with_vw_count(vw, counts != nullptr, [&](auto VW, auto COUNT) {
+        launch_ell_rp<VW, COUNT, kNodeRows, kNodeRows, true>(adj, n, d, words, (const u64*)s_in, (u64*)s_out, counts,
+                                                             lds, use_lds, 0, U, kNoSlices, st, ta);
+    });
     MJX_LAUNCH_CHECK("mjx_sweep_track_ell_rp");
     return MJX_OK;
 }
@@ -2110,16 +1887,11 @@ extern "C" int mjx_sweep_track_csr_rp(const int64_t* row_ptr, const int32_t* col
     if (rc) return rc;
     hipStream_t st = as_stream(stream);
     const int64_t U = units_of(words);
-    auto csr = [&](auto kern) {
-        const int g = resident_grid(kern, kBlock, lds, n * U);
-        kern<<<g, kBlock, lds, st>>>(nullptr, 0, row_ptr, col, order, n, words, (const u64*)s_in, (const u64*)s_prev,
-                                     (u64*)s_out, counts, use_lds, (u64*)diff, use_dlds, (int64_t)0, U);
-    };
-    if (vw == 2) {
-        if (counts) csr(k_sweep_track_gen_rp<2, true, true>); else csr(k_sweep_track_gen_rp<2, false, true>);
-    } else {
-        if (counts) csr(k_sweep_track_gen_rp<1, true, true>); else csr(k_sweep_track_gen_rp<1, false, true>);
-    }
+    with_vw_count(vw, counts != nullptr, [&](auto VW, auto COUNT) {
+        launch(k_sweep_gen_rp<VW, COUNT, true, kNodeRows, kNodeRows, true>, lds, n * U, st, nullptr, 0, row_ptr, col,
+               order, n, words, (const u64*)s_in, (u64*)s_out, counts, use_lds, (int64_t)0, U,
+               GeomArg<false>(kNoSlices), TrackArg<true>{(const u64*)s_prev, (u64*)diff, use_dlds});
+    });
     MJX_LAUNCH_CHECK("mjx_sweep_track_csr_rp");
     return MJX_OK;
 }

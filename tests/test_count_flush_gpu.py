@@ -213,9 +213,9 @@ def test_csr_counts_past_the_flush(mjx_mod, name):
 
 # (F, d, R, entry point)
 TRACK = {
-    "track_ell_d4_R4096": (255, 4, 4096, "ell"),      # k_sweep_track_ell_rp<4,2,true>
-    "track_gen_d5_R4000": (1023, 5, 4000, "ell"),     # k_sweep_track_gen_rp<1,true,false>
-    "track_csr_d4_R4000": (1023, 4, 4000, "csr"),     # k_sweep_track_gen_rp<1,true,true>
+    "track_ell_d4_R4096": (255, 4, 4096, "ell"),      # k_sweep_ell_rp<4,2,true>, TRACK
+    "track_gen_d5_R4000": (1023, 5, 4000, "ell"),     # k_sweep_gen_rp<1,true,false>, TRACK
+    "track_csr_d4_R4000": (1023, 4, 4000, "csr"),     # k_sweep_gen_rp<1,true,true>, TRACK
 }
 
 

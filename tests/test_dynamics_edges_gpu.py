@@ -313,6 +313,37 @@ def test_threshold_ladder_stars_replica_packed(mjx_mod, layout):
         assert torch.equal(mjx_mod.rollout(g, bits, T, words=W), out), T
 
 
+@pytest.mark.parametrize("layout", ["class", "csr"])
+@pytest.mark.parametrize("R", [192, 128])
+def test_row_tails_above_degree_8(mjx_mod, R, layout):
+    """The runtime-degree row body's tail at both unit widths: stars with hub
+    degrees 9, 10, 11, 13 (1, 2, 3, 1 neighbours after the four-wide steps)
+    and two isolated nodes, W = 3 (8-byte units) and W = 2 (16-byte units), on
+    k_sweep_cls_gen_rp (class) and k_sweep_gen_rp (csr), with and without the
+    fused count."""
+    u, v, pos = [], [], 0
+    for Dh in (9, 10, 11, 13):
+        u += [pos] * Dh
+        v += list(range(pos + 1, pos + 1 + Dh))
+        pos += Dh + 1
+    n = pos + 2
+    rp, col = mjx_mod.csr_from_edges(n, np.array(u), np.array(v))
+    g = mjx_mod.Graph.csr(rp, col)
+    assert g.class_ell()[2][:, 2].tolist() == [0, 1, 9, 10, 11, 13]
+    g.rp_layout = layout
+    W = R // 64
+    S0 = 2 * np.random.default_rng(R).integers(0, 2, (R, n)).astype(np.int64) - 1
+    bits = mjx_mod.pack(_cuda(S0))
+    for T in (1, 2):
+        want = orc.s_endstate_er(rp, col, S0, T, 1)
+        init = _init_counts(W)
+        cnt = init.clone()
+        out = mjx_mod.rollout(g, bits, T, words=W, counts=cnt)
+        assert np.array_equal(mjx_mod.unpack(out, n, R).cpu().numpy(), want), T
+        assert torch.equal(cnt - init, _plus(want)), T
+        assert torch.equal(mjx_mod.rollout(g, bits, T, words=W), out), T
+
+
 def test_threshold_ladder_stars_tracked(mjx_mod):
     from mjx import _lib as L, _device as D
     rp, col, S = _stars()
