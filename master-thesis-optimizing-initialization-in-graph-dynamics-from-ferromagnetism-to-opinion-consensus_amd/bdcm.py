@@ -322,18 +322,19 @@ def observables(chi, plan, p, c, attr_value, lmbd_in, epsilon=0.0):
     _sum(plan, zij, 1, 1)
     _sum(plan, mt, 0, 2)
     s = plan._sums.cpu().numpy()
-    phi = (s[0] - s[1] - lmbd_in * plan.n_iso) / plan.n
-    m_init = (s[2] + plan.n_iso) / plan.n
+    # an isolated node never moves, so it ends in the attractor only if it started there
+    phi = (s[0] - s[1] - int(attr_value) * lmbd_in * plan.n_iso) / plan.n
+    m_init = (s[2] + int(attr_value) * plan.n_iso) / plan.n
     return float(phi), float(m_init)
 
 
 def phi_BP_GENERAL_ER(chi, plan, p, c, attr_value, lmbd_in, epsilon=0.0):
-    """Free-entropy density (sum log Zi - sum log Zij - lmbd*n_iso)/n (nb:372-376)."""
+    """Free-entropy density (sum log Zi - sum log Zij - attr_value*lmbd*n_iso)/n (nb:372-376)."""
     return observables(chi, plan, p, c, attr_value, lmbd_in, epsilon)[0]
 
 
 def avg_m_init_GENERAL_ER(chi, plan, p, c, attr_value, epsilon=0.0):
-    """Mean initial magnetisation (nb:379-392)."""
+    """Mean initial magnetisation (sum of the edge terms + attr_value*n_iso)/n (nb:379-392)."""
     return observables(chi, plan, p, c, attr_value, 0.0, epsilon)[1]
 
 

@@ -300,8 +300,9 @@ def bdcm_observables_batch(chi, batch, p, c, attr_value, lmbd_in, epsilon=0.0):
         _lib.call("mjx_segsum_f64", _device.ptr(x), _device.ptr(seg), batch.G, take_log, _device.ptr(batch._work),
                   _device.ptr(batch._sums[slot]), st)
     s = batch._sums.cpu().numpy()
-    phi = (s[0] - s[1] - lmbd_in * batch.n_iso) / batch.n
-    m_init = (s[2] + batch.n_iso) / batch.n
+    # isolated nodes follow the attractor, as in bdcm.observables
+    phi = (s[0] - s[1] - int(attr_value) * lmbd_in * batch.n_iso) / batch.n
+    m_init = (s[2] + int(attr_value) * batch.n_iso) / batch.n
     return phi, m_init
 
 

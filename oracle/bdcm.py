@@ -155,25 +155,24 @@ def _dp(chi3, inc, ok, D, T):
     off = b @ pw
     S = (D + 1) ** T
     m = inc.shape[0]
-    LL = np.zeros((m, X, S))
+    va = np.flatnonzero(ok)                                # the x_a that end in the attractor
+    LL = np.zeros((S, m, va.size))                         # rho-major: a step moves whole contiguous rows
     if D == 0:
-        LL[:, :, 0] = 1.0
+        LL[0] = 1.0
     else:
-        M = chi3[inc]                                      # (m, D, X(xk), X(xa))
-        for k in range(X):
-            if ok[k]:
-                LL[:, :, off[k]] = M[:, 0, k, :]
+        M = chi3[inc][:, :, :, va]                         # (m, D, X(xk), valid xa)
+        for k in va:
+            LL[off[k]] = M[:, 0, k, :]
         digits = np.array(list(itertools.product(range(D + 1), repeat=T)), dtype=np.int64)
+        srcs = {k: np.nonzero(np.all(digits + b[k] <= D, axis=1))[0] for k in va}
         for Dm in range(1, D):
             L = np.zeros_like(LL)
-            for k in range(X):
-                if not ok[k]:
-                    continue
-                src = np.nonzero(np.all(digits + b[k] <= D, axis=1))[0]
-                L[:, :, src + off[k]] += LL[:, :, src] * M[:, Dm, k, :][:, :, None]
+            for k in va:
+                L[srcs[k] + off[k]] += LL[srcs[k]] * M[:, Dm, k, :][None, :, :]
             LL = L
-    LL[:, ~ok, :] = 0.0
-    return LL
+    out = np.zeros((m, X, S))
+    out[:, va, :] = LL.transpose(1, 2, 0)
+    return out
 
 
 def weights(T, lmbd_in):
@@ -253,15 +252,16 @@ def Zi_ER(chi, plan, p, c, attr_value, lmbd_in, epsilon=0.0):
 
 
 def phi_BP(chi, plan, p, c, attr_value, lmbd_in, epsilon=0.0):
-    """(sum log Zi - sum log Zij - lmbd*n_iso)/n (nb:372-376)."""
+    """(sum log Zi - sum log Zij - attr_value*lmbd*n_iso)/n (nb:372-376): an isolated
+    node never moves, so it ends in the attractor only if it started there."""
     zi = Zi_ER(chi, plan, p, c, attr_value, lmbd_in, epsilon)
     zij = Zij(chi, plan, p, c, attr_value, epsilon)
     with np.errstate(divide="ignore"):
-        return (np.sum(np.log(zi)) - np.sum(np.log(zij)) - lmbd_in * plan.n_iso) / plan.n
+        return (np.sum(np.log(zi)) - np.sum(np.log(zij)) - attr_value * lmbd_in * plan.n_iso) / plan.n
 
 
 def avg_m_init(chi, plan, p, c, attr_value, epsilon=0.0):
-    """nb:379-392."""
+    """nb:379-392; an isolated node contributes attr_value."""
     T = p + c
     s0 = (2 * traj01(T) - 1)[:, 0].astype(np.float64)
     prod = _pair_products(chi, plan, p, c, attr_value)
@@ -270,7 +270,7 @@ def avg_m_init(chi, plan, p, c, attr_value, epsilon=0.0):
     wgt = s0[None, :, None] / du[:, None, None] + s0[None, None, :] / dv[:, None, None]
     m = (wgt * prod).sum(axis=(1, 2))
     z = np.maximum(prod.sum(axis=(1, 2)), epsilon)
-    return (np.sum(m / z) + plan.n_iso) / plan.n
+    return (np.sum(m / z) + attr_value * plan.n_iso) / plan.n
 
 
 def entropy_procedure(chi, plan, p, c, attr_value, lambdas, damppar, eps=1e-6, T_max=1300, epsilon=0.0,

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from bdcm_cases import entry_err
 from conftest import GOLDEN, load_golden
 from oracle import bdcm as orc
 
@@ -38,19 +39,24 @@ def dev(x):
 def test_bdcm_sweep_and_observables_vs_reference(mjx_mod, name):
     z = load_golden(name)
     p, c, lm, damp = int(z["p"]), int(z["c"]), float(z["sweep_lmbd"]), float(z["damppar"])
+    av, epsilon = int(z["attr_value"]), float(z["epsilon"])
     plan = plan_of(mjx_mod, z)
     chi = dev(z["chi0"])
-    mjx_mod.bdcm_leaf_reset(chi, plan, p, c, 1, lm)
+    mjx_mod.bdcm_leaf_reset(chi, plan, p, c, av, lm)
     assert rowrel(chi.cpu().numpy(), z["sweep_leaf"]) < 1e-14
+    assert entry_err(chi.cpu().numpy(), z["sweep_leaf"]) <= 1e-12
     chi = dev(z["sweep_leaf"])
-    out = mjx_mod.BDCM_ER(chi, plan, p, c, 1, lm, damp)
+    out = mjx_mod.BDCM_ER(chi, plan, p, c, av, lm, damp, epsilon)
     assert out is chi                                   # in place, like nb:196-198
     assert rowrel(chi.cpu().numpy(), z["sweep_chi"]) < 1e-12
+    assert entry_err(chi.cpu().numpy(), z["sweep_chi"]) <= 1e-12
     ref = dev(z["sweep_chi"])
-    np.testing.assert_allclose(mjx_mod.Zi_ER(ref, plan, p, c, 1, lm).cpu().numpy(), z["sweep_zi"], rtol=1e-12, atol=0)
-    np.testing.assert_allclose(mjx_mod.Zij(ref, plan, p, c, 1).cpu().numpy(), z["sweep_zij"], rtol=1e-12, atol=0)
-    assert abs(mjx_mod.phi_BP_GENERAL_ER(ref, plan, p, c, 1, lm) - float(z["sweep_phi"])) < 1e-12
-    assert abs(mjx_mod.avg_m_init_GENERAL_ER(ref, plan, p, c, 1) - float(z["sweep_m_init"])) < 1e-12
+    np.testing.assert_allclose(mjx_mod.Zi_ER(ref, plan, p, c, av, lm, epsilon).cpu().numpy(), z["sweep_zi"],
+                               rtol=1e-12, atol=0)
+    np.testing.assert_allclose(mjx_mod.Zij(ref, plan, p, c, av, epsilon).cpu().numpy(), z["sweep_zij"],
+                               rtol=1e-12, atol=0)
+    assert abs(mjx_mod.phi_BP_GENERAL_ER(ref, plan, p, c, av, lm, epsilon) - float(z["sweep_phi"])) < 1e-12
+    assert abs(mjx_mod.avg_m_init_GENERAL_ER(ref, plan, p, c, av, epsilon) - float(z["sweep_m_init"])) < 1e-12
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -60,7 +66,8 @@ def test_bdcm_entropy_procedure_vs_reference(mjx_mod, name):
     plan = plan_of(mjx_mod, z)
     chi = dev(z["chi0"])
     res = mjx_mod.BDCM_entropy_procedure_GENERAL_ER(chi, plan, z["lambdas"], T_max=int(z["T_max"]), p=p, c=c,
-                                                    eps=float(z["eps"]), damppar=float(z["damppar"]))
+                                                    attr_value=int(z["attr_value"]), eps=float(z["eps"]),
+                                                    damppar=float(z["damppar"]), epsilon=float(z["epsilon"]))
     L = len(z["iters"])
     assert np.array_equal(res["iters"][:L], z["iters"])
     for k in ("m_init", "ent1", "ent"):
@@ -68,6 +75,7 @@ def test_bdcm_entropy_procedure_vs_reference(mjx_mod, name):
         np.testing.assert_allclose(res[k], z[k], rtol=1e-9, atol=1e-12)
     assert res["counts"] == z["counts"]
     assert rowrel(chi.cpu().numpy(), z["chi_final"]) < 1e-9
+    assert entry_err(chi.cpu().numpy(), z["chi_final"]) <= 1e-9
 
 
 @pytest.mark.parametrize("p,c,deg", [(1, 1, 5.0), (2, 1, 3.0), (1, 2, 3.0), (2, 2, 2.0), (3, 1, 2.0),
@@ -76,7 +84,7 @@ def test_bdcm_random_graph_vs_oracle(mjx_mod, p, c, deg):
     """Own ER graphs (hubs up to degree ~14, leaves, all T <= 4) against the
     oracle: one leaf reset + sweep, Zi, Zij, phi, m_init.  No seed re-rolling:
     classes whose count table exceeds the LDS budget (T = 4 beyond 6 incoming
-    messages, T = 3 beyond 12) run from the global scratch slab."""
+    messages, T = 3 beyond 16, T = 2 beyond 99) run from the global scratch slab."""
     n = 2000 if p + c <= 3 else (500 if deg < 5 else 200)     # the oracle's T = 4 tables grow as (D+1)^4
     plan = mjx_mod.bdcm_er_plan(n, deg / (n - 1), seed=7 * p + c)
     lib = mjx_mod.load_library()
