@@ -1005,6 +1005,61 @@ int mjx_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p,
                    int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
                    int32_t* flag, void* stream);
 
+/* ---- census of the minimal consensus sets -------------------------------- */
+/*
+ * The rule is monotone, so U_t = {x : onestep^t(x) is all +1}, the set that
+ * counts[t] counts, is an up-set: raising a spin keeps x in it.  Its minimal
+ * elements are the local minima of a greedy quench at T = t: consensus
+ * configurations from which no single +1 node can be dropped.  With
+ * T = p + c - 1 and t = 0..T:
+ *   Mask: mask[t][b] is a 64-bit word; bit j is set iff configuration
+ *     x = 64 b + j is in U_t.  For n < 6 only the first 2^n bits of block 0 can
+ *     be set.  Layout (T+1, B) words, B = 2^max(n-6, 0): (T+1) 2^n / 8 bytes,
+ *     2 GiB at n = 32, T = 3.
+ *   Minimal set: M_t = {x in U_t : x without i is not in U_t for every +1 node
+ *     i of x}; minima[t][k] = #{x in M_t : popcount(x) = k}.
+ *   Heaviest minimum: for each t the x in M_t with the largest (popcount(x), x),
+ *     as the key k << 48 | x under an atomic max.  The key starts at 0, which
+ *     no minimum has: all -1 is a fixed point and never reaches all +1.
+ *   Lightest minimum: the witness of the census.
+ * So minima[t][min_plus[t]] = counts[t][min_plus[t]], minima[t] <= counts[t]
+ * elementwise, and minima[0] is 1 at k = n and 0 elsewhere.
+ *
+ * Pass 1, mjx_census_mask_ell / _csr: mjx_census_ell / _csr (same enumeration,
+ * counts, witness keys, flag and status codes) that also stores the word of
+ * every block b of [block_lo, block_hi) at mask[t B + b] for every t = 0..T,
+ * one plain vector store per lane and level -- the zero words and the full
+ * blocks the enumeration does not sweep included, so the caller does not
+ * zero the buffer.  mask: device [(T+1) B] words, NULL is MJX_EINVAL.  When
+ * the flag comes back set the mask is void like the counts.
+ *
+ * Pass 2, mjx_census_minima, needs no graph: it counts the minimal elements of
+ * the levels of any such bitmap whose levels are up-sets.  A wave owns 64
+ * consecutive blocks (lane = the low six bits of b) and looks x without node v
+ * up inside its own word (v < 6), in the word of lane ^ 2^(v-6) (v < 12) and in
+ * the 64 consecutive words at (b & ~63) ^ 2^(v-6) (v >= 12, one coalesced
+ * 512-byte row, read only where that bit of b is set); a wave whose 64 words
+ * are all zero at a level reads nothing more.  A block reads only blocks of
+ * lower index, at most 2^(n-3) (1 + (n-12)/2) bytes per level; they must
+ * have been written, whatever range this call covers.
+ * minima: device [T+1][n+1], ADDED to (64-bit atomics); heaviest_key: device
+ * [T+1], atomic-max'ed into (the caller starts it at 0); so [0, B) may be
+ * split over launches into the same buffers.  A wave's 64 blocks go together:
+ * block_lo must be a multiple of 64 and block_hi a multiple of 64 or B.
+ * grid: 0 = the library's choice (a resident grid-stride loop), > 0 forces the
+ * number of one-wave workgroups.  MJX_ERANGE: n > 48, T > 6.  MJX_EINVAL: n < 1,
+ * T < 0, a block range outside 0 <= block_lo <= block_hi <= B or not aligned
+ * as above, grid < 0, a NULL pointer.  No allocation, no host synchronisation.
+ */
+int mjx_census_mask_ell(const int32_t* adj, int64_t n, int d, int p, int c, int64_t block_lo, int64_t block_hi,
+                        int grid, unsigned long long* counts, unsigned long long* witness_key, int32_t* flag,
+                        uint64_t* mask, void* stream);
+int mjx_census_mask_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t block_lo,
+                        int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
+                        int32_t* flag, uint64_t* mask, void* stream);
+int mjx_census_minima(const uint64_t* mask, int64_t n, int T, int64_t block_lo, int64_t block_hi, int grid,
+                      unsigned long long* minima, unsigned long long* heaviest_key, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

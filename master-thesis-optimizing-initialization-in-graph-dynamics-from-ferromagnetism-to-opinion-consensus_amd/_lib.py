@@ -159,6 +159,9 @@ SIGNATURES = {
     "mjx_census_lds": [c_i64],
     "mjx_census_ell": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp],
+    "mjx_census_mask_ell": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_census_mask_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_census_minima": [c_vp, c_i64, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "mjx_last_hip_error": ctypes.c_char_p,
              "mjx_sa_lightcone_lds": c_i64, "mjx_sa_lds_bytes": c_i64, "mjx_sa_lds_plan": c_i64, "mjx_bdcm_lds_bytes": c_i64, "mjx_bdcm_scratch_bytes": c_i64,

@@ -16,6 +16,9 @@ the kernel (csrc/mjx_census.hip: a lane per block of 64 configurations, the
 levels in LDS), so the enumeration moves no memory; the host only splits the
 blocks over launches of at most ``chunk_blocks`` each.
 
+``census_minima`` keeps the membership bit of every x and counts, from that
+bitmap, the minimal elements of every level: the local minima of the quenches.
+
 Not covered: several devices (the block range makes it a host loop), n > 48,
 symmetry reduction.  There is no CPU fallback.
 """
@@ -81,25 +84,66 @@ def _check_rows(rows, n):
                          "defined for undirected graphs")
 
 
-def _run(g, p, c, block_lo, block_hi, chunk, grid):
+def _run(g, p, c, block_lo, block_hi, chunk, grid, mask=None):
     """Blocks [block_lo, block_hi) in launches of at most ``chunk`` blocks -> (counts int64 (T+1, n+1), keys
-    int64 (T+1,): the witness keys as signed words), device tensors."""
+    int64 (T+1,): the witness keys as signed words), device tensors.  ``mask``: a device int64 (T+1, B)
+    tensor that receives the membership words of the blocks (the mask entry points)."""
     n, T = g.n, p + c - 1
     dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
     counts = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=dev)
     keys = torch.full((T + 1,), -1, dtype=torch.int64, device=dev)           # all ones
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    kept = "" if mask is None else "mask_"
     if g.kind == "ell":
-        name, ga = "mjx_census_ell", (_device.ptr(g.adj) if g.d else None, n, g.d)
+        name, ga = f"mjx_census_{kept}ell", (_device.ptr(g.adj) if g.d else None, n, g.d)
     else:
-        name, ga = "mjx_census_csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n)
+        name, ga = f"mjx_census_{kept}csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n)
     st = _device.stream_handle()
+    out = (_device.ptr(counts), _device.ptr(keys), _device.ptr(flag)) + (() if mask is None else (_device.ptr(mask),))
     for lo in range(block_lo, block_hi, chunk):
-        _lib.call(name, *ga, p, c, lo, min(block_hi, lo + chunk), grid, _device.ptr(counts), _device.ptr(keys),
-                  _device.ptr(flag), st)
+        _lib.call(name, *ga, p, c, lo, min(block_hi, lo + chunk), grid, *out, st)
     if int(flag.item()):
         raise _lib.MjxError("census: an adjacency entry lies outside 0..n-1 or a row is longer than 47")
     return counts, keys
+
+
+def _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=False):
+    """The host refusals of ``census`` -> (graph, p, c, n, blocks, chunk, grid); ``mask``: the refusal of a
+    large 2^n names the bytes of the bitmap."""
+    p, c, T = _steps(p, c)
+    grid = _kernel_options(kernel)
+    n = _host_n(graph)
+    if n < 1:
+        raise ValueError("census: the graph has no nodes")
+    if n > N_MAX:
+        raise ValueError(f"census: n = {n} nodes; the enumeration is limited to n <= {N_MAX}")
+    configs = 1 << n
+    if configs > int(max_configs):
+        raise ValueError(f"census: 2^{n} = {configs} configurations exceed max_configs = {int(max_configs)}"
+                         + (f"; the bitmap of the {T + 1} levels would take (T+1) * 2^n / 8 = "
+                            f"{(T + 1) * max(configs, 64) // 8} bytes" if mask else ""))
+    blocks = 1 << max(n - 6, 0)
+    chunk = CHUNK_BLOCKS if chunk_blocks is None else int(chunk_blocks)
+    if chunk < 1:
+        raise ValueError("chunk_blocks must be >= 1")
+    _check_rows(_host_rows(graph), n)
+    return as_graph(graph), p, c, n, blocks, chunk, grid
+
+
+def _spins(key, n):
+    """The configurations of keys k << 48 | x as +-1 rows, int8 (len(key), n)."""
+    x = key & np.uint64((1 << 48) - 1)
+    bits = (x[:, None] >> np.arange(n, dtype=np.uint64)[None, :]) & np.uint64(1)
+    return np.where(bits == 1, 1, -1).astype(np.int8)
+
+
+def _levels(cnt, key, n):
+    """Counts and witness keys of the levels -> the result dict of ``census``."""
+    min_plus = (key >> np.uint64(48)).astype(np.int64)
+    with np.errstate(divide="ignore"):
+        entropy = np.log(cnt.astype(np.float64)) / n
+    return {"counts": cnt, "min_plus": min_plus, "m_min": (2 * min_plus - n) / n, "witness": _spins(key, n),
+            "entropy": entropy, "configs": 1 << n}
 
 
 def census(graph, p, c, *, max_configs=2 ** 36, chunk_blocks=None, kernel=None):
@@ -118,30 +162,59 @@ def census(graph, p, c, *, max_configs=2 ** 36, chunk_blocks=None, kernel=None):
     ``entropy`` float64 (T+1, n+1) (-inf where the count is 0) and ``configs``
     = 2^n.  Level 0 counts the all +1 configuration alone, so every level has a
     witness."""
-    p, c, T = _steps(p, c)
-    grid = _kernel_options(kernel)
-    n = _host_n(graph)
-    if n < 1:
-        raise ValueError("census: the graph has no nodes")
-    if n > N_MAX:
-        raise ValueError(f"census: n = {n} nodes; the enumeration is limited to n <= {N_MAX}")
-    configs = 1 << n
-    if configs > int(max_configs):
-        raise ValueError(f"census: 2^{n} = {configs} configurations exceed max_configs = {int(max_configs)}")
-    blocks = 1 << max(n - 6, 0)
-    chunk = CHUNK_BLOCKS if chunk_blocks is None else int(chunk_blocks)
-    if chunk < 1:
-        raise ValueError("chunk_blocks must be >= 1")
-    _check_rows(_host_rows(graph), n)
-    counts, keys = _run(as_graph(graph), p, c, 0, blocks, chunk, grid)
-    cnt = counts.cpu().numpy()
+    g, p, c, n, blocks, chunk, grid = _checked(graph, p, c, max_configs, chunk_blocks, kernel)
+    counts, keys = _run(g, p, c, 0, blocks, chunk, grid)
     key = keys.cpu().numpy().view(np.uint64)
     if (key == np.uint64(0xFFFFFFFFFFFFFFFF)).any():                        # every level counts all +1 at least
         raise _lib.MjxError("census: a level without a witness")
-    min_plus = (key >> np.uint64(48)).astype(np.int64)
-    x = key & np.uint64((1 << 48) - 1)
-    bits = (x[:, None] >> np.arange(n, dtype=np.uint64)[None, :]) & np.uint64(1)
-    with np.errstate(divide="ignore"):
-        entropy = np.log(cnt.astype(np.float64)) / n
-    return {"counts": cnt, "min_plus": min_plus, "m_min": (2 * min_plus - n) / n,
-            "witness": np.where(bits == 1, 1, -1).astype(np.int8), "entropy": entropy, "configs": configs}
+    return _levels(counts.cpu().numpy(), key, n)
+
+
+def census_minima(graph, p, c, *, max_configs=2 ** 34, chunk_blocks=None, kernel=None, return_mask=False):
+    """``census`` and, for every level t, the census of its minimal consensus
+    sets M_t: the configurations that are all +1 after t steps and from which
+    no single +1 node can be dropped -- the local minima a greedy quench at
+    T = t can end in (``quench``, ``quench_restarts``), all of them, by weight.
+
+    Arguments as for ``census``.  Pass 1 is the census that keeps the bit "x is
+    all +1 after t steps" of every x and level in a device bitmap of
+    (T+1) * 2^n / 8 bytes (2 GiB at n = 32, T = 3: hence the smaller default of
+    ``max_configs``, whose refusal names the bytes); pass 2 counts the minimal
+    elements from the bitmap alone (mjx_census_minima, include/mjx.h).  Both
+    run on the current stream in launches of at most ``chunk_blocks`` blocks,
+    pass 2 in multiples of 64 blocks; ``kernel``: ``{"grid": g}`` forces the
+    workgroups of both.
+
+    Returns the dict of ``census`` (same values) and ``minima`` int64
+    (T+1, n+1), ``minima_total`` int64 (T+1,), ``max_plus`` int64 (T+1,) with
+    ``m_max`` = (2 max_plus - n) / n and ``witness_max`` int8 (T+1, n): the
+    minimum with the largest (weight, x); ``mean_plus`` float64 (T+1,) =
+    sum k minima / sum minima.  The lightest minimum is ``witness``, and
+    ``minima[t, min_plus[t]] == counts[t, min_plus[t]]``.  ``return_mask``:
+    also ``mask``, the device bitmap as int64 bit patterns (T+1, B),
+    B = 2^max(n-6, 0): bit j of word b of level t is configuration 64 b + j."""
+    g, p, c, n, blocks, chunk, grid = _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=True)
+    T = p + c - 1
+    dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
+    mask = torch.empty((T + 1, blocks), dtype=torch.int64, device=dev)       # pass 1 writes every word
+    counts, keys = _run(g, p, c, 0, blocks, chunk, grid, mask=mask)
+    minima = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=dev)
+    heavy = torch.zeros((T + 1,), dtype=torch.int64, device=dev)
+    st = _device.stream_handle()
+    rows = -(-chunk // 64) * 64                                              # a wave's 64 blocks go together
+    for lo in range(0, blocks, rows):
+        _lib.call("mjx_census_minima", _device.ptr(mask), n, T, lo, min(blocks, lo + rows), grid,
+                  _device.ptr(minima), _device.ptr(heavy), st)
+    key = keys.cpu().numpy().view(np.uint64)
+    top = heavy.cpu().numpy().view(np.uint64)
+    if (key == np.uint64(0xFFFFFFFFFFFFFFFF)).any() or (top == 0).any():    # all +1 is in every level
+        raise _lib.MjxError("census_minima: a level without a minimum")
+    res = _levels(counts.cpu().numpy(), key, n)
+    mn = minima.cpu().numpy()
+    max_plus = (top >> np.uint64(48)).astype(np.int64)
+    res.update(minima=mn, minima_total=mn.sum(axis=1), max_plus=max_plus, m_max=(2 * max_plus - n) / n,
+               witness_max=_spins(top, n),
+               mean_plus=(mn * np.arange(n + 1)[None, :]).sum(axis=1) / mn.sum(axis=1))
+    if return_mask:
+        res["mask"] = mask
+    return res

@@ -34,7 +34,9 @@ and write its np.savez keys.
         one small random regular or Erdos-Renyi graph (n <= 48, isolated nodes
         kept), every one of the 2^n starts run p + c - 1 steps; output
         "census_{graph}.npz": counts, min_plus, m_min, witness, entropy,
-        configs, edges
+        configs, edges.  ``--minima`` adds the census of the minimal consensus
+        sets, the local minima of the quenches (census.census_minima): minima,
+        minima_total, max_plus, m_max, witness_max, mean_plus
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -197,7 +199,11 @@ def build_parser():
     ce.add_argument("--graph-seed", type=int, default=0, help="seed of the graph")
     ce.add_argument("--p", type=int, required=True)
     ce.add_argument("--c", type=int, required=True)
-    ce.add_argument("--max-configs", type=int, default=2 ** 36, help="refuse a larger 2^n")
+    ce.add_argument("--max-configs", type=int, default=None,
+                    help="refuse a larger 2^n (default 2^36; 2^34 with --minima, whose bitmap takes (T+1) 2^n / 8 "
+                         "bytes)")
+    ce.add_argument("--minima", action="store_true",
+                    help="also count the minimal consensus sets of every level, the local minima of the quenches")
     ce.add_argument("--out", default=None, help="output .npz (default: census_{graph}.npz)")
     return ap
 
@@ -396,7 +402,7 @@ def run_quench(a):
 
 
 def run_census(a):
-    from .census import census
+    from .census import census, census_minima
     from .graph import Graph, erdos_renyi, random_regular_graph
     t0 = time.time()
     if a.graph == "rrg":
@@ -409,7 +415,8 @@ def run_census(a):
         g = Graph.csr(rp, col)
         u = np.repeat(np.arange(a.n), np.diff(rp))
         v = np.asarray(col)
-    res = census(g, a.p, a.c, max_configs=a.max_configs)
+    limit = {} if a.max_configs is None else {"max_configs": a.max_configs}
+    res = (census_minima if a.minima else census)(g, a.p, a.c, **limit)
     keep = u < v
     res["edges"] = np.stack([u[keep], v[keep]], axis=1).astype(np.int64)
     out = a.out or f"census_{a.graph}.npz"
@@ -417,6 +424,10 @@ def run_census(a):
     print(f"census: {a.graph} n={a.n}, 2^{a.n} configurations, p={a.p} c={a.c}: min_plus "
           f"{res['min_plus'].tolist()}, m_min {np.round(res['m_min'], 4).tolist()}, reached "
           f"{res['counts'].sum(axis=1).tolist()}, {time.time() - t0:.1f} s -> {out}", flush=True)
+    if a.minima:
+        print(f"census: minimal consensus sets {res['minima_total'].tolist()}, of them optimal "
+              f"{[int(res['minima'][t, k]) for t, k in enumerate(res['min_plus'])]}, max_plus "
+              f"{res['max_plus'].tolist()}, mean_plus {np.round(res['mean_plus'], 3).tolist()}", flush=True)
     return res
 
 

@@ -15,6 +15,10 @@
 // adjacency sits in LDS as bytes (n <= 48) behind u16 row offsets.
 //
 // The workgroup is one wave.  Everything is integer; no flags needed.
+//
+// k_census<Adj, true> also keeps the membership bits: the word `mask` of
+// every block and level goes to mask[t * B + b], the input of k_census_minima
+// below, which counts the minimal elements of every level from that bitmap.
 #include "mjx_common.h"
 #include <algorithm>
 
@@ -132,6 +136,14 @@ __device__ __forceinline__ u64 cn_min64(u64 x) {
     return x;
 }
 
+__device__ __forceinline__ u64 cn_max64(u64 x) {
+    for (int off = 32; off; off >>= 1) {
+        const u64 o = (u64)__shfl_xor((long long)x, off);
+        x = o > x ? o : x;
+    }
+    return x;
+}
+
 // One sweep: level lv (>= 1) of the lane's block from level lv-1.  FIRST: the
 // source is level 0, generated from b and the pattern table `src` (n words;
 // b < 2^42, so bit (u + 58) mod 64 of b is bit u-6 for u >= 6 and 0 below);
@@ -179,10 +191,12 @@ __device__ __forceinline__ u64 cn_sweep(int n, int fixed, const uint16_t* __rest
     return all;
 }
 
-template <class Adj>
+// MASK: the level's word of every block of the range is stored at bits[t * B + b], the words of the
+// levels that are not swept (zero words, full blocks) included; without it no mask code is compiled
+template <class Adj, bool MASK>
 __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo, u64 block_hi,
                                                u64* __restrict__ counts, u64* __restrict__ witness,
-                                               int32_t* __restrict__ flag) {
+                                               int32_t* __restrict__ flag, u64* __restrict__ bits) {
     extern __shared__ __align__(8) unsigned char cn_smem[];
     const CnLds L = cn_lds(n);
     u64* buf = (u64*)cn_smem;
@@ -210,6 +224,7 @@ __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo
     const u64 last_block = n > 6 ? (1ull << (n - 6)) - 1 : 0;
     const u64 last_bit = 1ull << ((n < 6 ? (1 << n) : 64) - 1);
     const u64 stride = (u64)gridDim.x * 64;
+    const u64 B = last_block + 1;
     for (u64 first = block_lo + (u64)blockIdx.x * 64; first < block_hi; first += stride) {
         const u64 b = first + lane;
         const bool active = b < block_hi;
@@ -225,6 +240,7 @@ __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo
                                          : cn_sweep<false>(n, fixed, off, nbr, src, dst, b, lane);
                 mask = active ? (all & valid) : 0;
             }
+            if (MASK && active) bits[(u64)t * B + b] = mask;
             if (__ballot(mask != 0) == 0) continue;
             u64 key = ~0ull;                                         // of the first weight that has a configuration
 #pragma unroll
@@ -245,10 +261,86 @@ __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo
     if (lane <= T && best[lane] != ~0ull) atomicMin(&witness[lane], best[lane]);
 }
 
+// The minimal elements of a bitmap's levels (definitions in include/mjx.h).  A wave owns the 64
+// consecutive blocks first .. first + 63 (first a multiple of 64, so lane = the low six bits of b) and
+// builds r, the word of the configurations that stay in the set when some +1 node v is dropped, from the
+// words of the blocks b with bit v cleared: inside its own word (v < 6), in lane ^ 2^(v-6) (v < 12),
+// and in the row of 64 words at first ^ 2^(v-6) (v >= 12: that bit of b is the same in the whole wave,
+// four such rows are loaded together).  Minimal is mask & ~r.
+constexpr int CN_MIN_ROWS = 4;
+
+__global__ void __launch_bounds__(64) k_census_minima(const u64* __restrict__ bits, int n, int T, u64 block_lo,
+                                                      u64 block_hi, u64* __restrict__ minima,
+                                                      u64* __restrict__ heaviest) {
+    __shared__ u64 hist[(CN_MAXT + 1) * (CN_MAXN + 1)];
+    __shared__ u64 best[CN_MAXT + 1];                                // largest key of level t in this workgroup
+    const int lane = threadIdx.x;
+    const int cells = (T + 1) * (n + 1);
+    for (int i = lane; i < cells; i += 64) hist[i] = 0;
+    if (lane <= CN_MAXT) best[lane] = 0;
+    __syncthreads();
+
+    const u64 valid = n < 6 ? ((1ull << (1 << n)) - 1) : ~0ull;
+    const u64 B = 1ull << (n > 6 ? n - 6 : 0);
+    const int in_word = n < 6 ? n : 6, in_wave = n < 12 ? n : 12;
+    const u64 stride = (u64)gridDim.x * 64;
+    for (u64 first = block_lo + (u64)blockIdx.x * 64; first < block_hi; first += stride) {
+        const u64 b = first + lane;
+        const bool active = b < block_hi;                            // a last row shorter than 64: B < 64
+        const int kb = __popcll(b);
+#pragma unroll 1
+        for (int t = 0; t <= T; ++t) {
+            const u64* row = bits + (u64)t * B;
+            const u64 m = active ? row[b] & valid : 0;
+            if (__ballot(m != 0) == 0) continue;                     // nothing counted here: no neighbour is read
+            u64 r = 0;
+            for (int v = 0; v < in_word; ++v) r |= (m << (1 << v)) & cn_pattern(v);
+            for (int v = 6; v < in_wave; ++v) {
+                const u64 o = (u64)__shfl_xor((long long)m, 1 << (v - 6));
+                r |= ((lane >> (v - 6)) & 1) ? o : 0;
+            }
+            // the set bits of first >> 6 are the nodes v >= 12 that are +1 in the whole wave; the partner
+            // rows lie below first, inside [0, B).  A round without a node left reads the own row again.
+            u64 up = first >> 6;
+            while (up && __ballot((m & ~r) != 0)) {
+                u64 o[CN_MIN_ROWS];
+#pragma unroll
+                for (int i = 0; i < CN_MIN_ROWS; ++i) {
+                    const u64 bit = up & (0 - up);
+                    up ^= bit;
+                    const u64 w = row[(first ^ (bit << 6)) + lane];
+                    o[i] = bit ? w : 0;
+                }
+#pragma unroll
+                for (int i = 0; i < CN_MIN_ROWS; ++i) r |= o[i];
+            }
+            const u64 least = m & ~r;
+            if (__ballot(least != 0) == 0) continue;
+            u64 key = 0;                                             // of the last weight that has a minimum
+#pragma unroll
+            for (int w = 0; w <= 6; ++w) {
+                const u64 x = least & cn_weight(w);
+                if (x) {
+                    atomicAdd(&hist[t * (n + 1) + kb + w], (u64)__popcll(x));
+                    key = ((u64)(kb + w) << 48) | (b * 64 + (u64)(63 - __builtin_clzll(x)));
+                }
+            }
+            key = cn_max64(key);
+            if (lane == 0) atomicMax(&best[t], key);
+        }
+    }
+    __syncthreads();
+    for (int i = lane; i < cells; i += 64)
+        if (hist[i]) atomicAdd(&minima[i], hist[i]);
+    if (lane <= T && best[lane]) atomicMax(&heaviest[lane], best[lane]);
+}
+
 template <class Adj>
 static int census_run(Adj A, int64_t n, int p, int c, int64_t block_lo, int64_t block_hi, int grid,
-                      unsigned long long* counts, unsigned long long* witness_key, int32_t* flag, void* stream) {
+                      unsigned long long* counts, unsigned long long* witness_key, int32_t* flag, bool keep,
+                      uint64_t* mask, void* stream) {
     if (p < 0 || c < 0 || p + c - 1 < 0 || n < 1 || !counts || !witness_key || !flag || grid < 0) return MJX_EINVAL;
+    if (keep && !mask) return MJX_EINVAL;
     if (n > CN_MAXN || p + c - 1 > CN_MAXT) return MJX_ERANGE;
     const int64_t B = (int64_t)1 << (n > 6 ? n - 6 : 0);
     if (block_lo < 0 || block_lo > block_hi || block_hi > B) return MJX_EINVAL;
@@ -261,8 +353,12 @@ static int census_run(Adj A, int64_t n, int p, int c, int64_t block_lo, int64_t 
         const int64_t per = std::min<int64_t>(32, (int64_t)(kCnLdsPerCu / lds));
         g = (int)std::max<int64_t>(1, std::min<int64_t>((block_hi - block_lo + 63) / 64, device_cus() * per));
     }
-    k_census<Adj><<<(unsigned)g, 64, lds, as_stream(stream)>>>(A, (int)n, p + c - 1, (u64)block_lo, (u64)block_hi,
-                                                             counts, witness_key, flag);
+    if (keep)
+        k_census<Adj, true><<<(unsigned)g, 64, lds, as_stream(stream)>>>(
+            A, (int)n, p + c - 1, (u64)block_lo, (u64)block_hi, counts, witness_key, flag, (u64*)mask);
+    else
+        k_census<Adj, false><<<(unsigned)g, 64, lds, as_stream(stream)>>>(
+            A, (int)n, p + c - 1, (u64)block_lo, (u64)block_hi, counts, witness_key, flag, nullptr);
     MJX_LAUNCH_CHECK("k_census");
     return MJX_OK;
 }
@@ -282,12 +378,47 @@ extern "C" int mjx_census_ell(const int32_t* adj, int64_t n, int d, int p, int c
                               void* stream) {
     if (d < 0 || (d > 0 && !adj)) return MJX_EINVAL;
     if (d > CN_MAXDEG) return MJX_ERANGE;
-    return census_run(CnEll{adj, d}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, stream);
+    return census_run(CnEll{adj, d}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, false, nullptr,
+                      stream);
 }
 
 extern "C" int mjx_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t block_lo,
                               int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
                               int32_t* flag, void* stream) {
     if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
-    return census_run(CnCsr{row_ptr, col}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, stream);
+    return census_run(CnCsr{row_ptr, col}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, false,
+                      nullptr, stream);
+}
+
+extern "C" int mjx_census_mask_ell(const int32_t* adj, int64_t n, int d, int p, int c, int64_t block_lo,
+                                   int64_t block_hi, int grid, unsigned long long* counts,
+                                   unsigned long long* witness_key, int32_t* flag, uint64_t* mask, void* stream) {
+    if (d < 0 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (d > CN_MAXDEG) return MJX_ERANGE;
+    return census_run(CnEll{adj, d}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, true, mask, stream);
+}
+
+extern "C" int mjx_census_mask_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c,
+                                   int64_t block_lo, int64_t block_hi, int grid, unsigned long long* counts,
+                                   unsigned long long* witness_key, int32_t* flag, uint64_t* mask, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;
+    return census_run(CnCsr{row_ptr, col}, n, p, c, block_lo, block_hi, grid, counts, witness_key, flag, true, mask,
+                      stream);
+}
+
+extern "C" int mjx_census_minima(const uint64_t* mask, int64_t n, int T, int64_t block_lo, int64_t block_hi, int grid,
+                                 unsigned long long* minima, unsigned long long* heaviest_key, void* stream) {
+    if (!mask || !minima || !heaviest_key || n < 1 || T < 0 || grid < 0) return MJX_EINVAL;
+    if (n > CN_MAXN || T > CN_MAXT) return MJX_ERANGE;
+    const int64_t B = (int64_t)1 << (n > 6 ? n - 6 : 0);
+    if (block_lo < 0 || block_lo > block_hi || block_hi > B) return MJX_EINVAL;
+    if (block_lo % 64 || (block_hi % 64 && block_hi != B)) return MJX_EINVAL;    // a wave's 64 blocks go together
+    if (block_lo == block_hi) return MJX_OK;
+    // a resident grid-stride loop: 2.8 KiB of LDS and few registers, so 8 one-wave workgroups a SIMD
+    const int64_t rows = (block_hi - block_lo + 63) / 64;
+    const int g = grid ? grid : (int)std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)device_cus() * 32));
+    k_census_minima<<<(unsigned)g, 64, 0, as_stream(stream)>>>((const u64*)mask, (int)n, T, (u64)block_lo,
+                                                               (u64)block_hi, minima, heaviest_key);
+    MJX_LAUNCH_CHECK("k_census_minima");
+    return MJX_OK;
 }
