@@ -955,6 +955,69 @@ int mjx_quench_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, i
                         uint64_t* out_np, int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag,
                         void* stream);
 
+/* ---- the (1, 2) exchange descent behind the quench jobs -------------------- */
+/*
+ * A quench ends in a single-flip local minimum.  The smallest move that leaves
+ * one downwards is a (1, 2) exchange: turn one -1 spin to +1 (consensus is
+ * kept, the rule is monotone), then drop two +1 spins.  Per job (start r, order
+ * k; jobs, orders, graphs, s_np, caps and the first outputs as mjx_quench_jobs_*),
+ * with consensus(z) = "onestep^T(z) is all +1":
+ *
+ *   x = start
+ *   if not consensus(x): result = start, flipped = exchanges = passes = 0,
+ *                        converged = 1
+ *   x = the quench pass over ord (flipped = its count); plus_quench = +1 spins of x
+ *   for pass = 1 .. max_passes:
+ *       moved = false
+ *       for j in ord, with x[j] = -1 at its turn:
+ *           y = x with y[j] = +1; dropped = 0
+ *           for a in ord, a != j, y[a] = +1 at its turn:
+ *               if consensus(y with y[a] = -1): y[a] = -1, dropped += 1
+ *           if dropped >= 2: x = y, exchanges += 1, moved = true
+ *           (dropped = 1, a swap of equal weight, and dropped = 0 leave x as it was)
+ *       passes = pass
+ *       if not moved: converged = 1, stop
+ *
+ * converged = the last pass committed nothing (the greedy inner walk can take a
+ * single drop that blocks a pair, so it does not say that no pair exists).  x
+ * stays a single-flip local minimum; every exchange lowers the weight by at
+ * least 1.  T = 0 returns the start (passes = 1 with consensus).
+ *
+ * The kernel tries fewer nodes with the same result (DESIGN.md has the proof):
+ * with D_t the nodes whose level-t value the add of j changed (t < T; D_0 =
+ * {j}), only a +1 node within t + 2 hops of some D_t can be dropped after the
+ * add that could not be dropped before.  These candidates lie in the ball of
+ * radius 2T around j; cap2T bounds that ball (mjx_ell_ball_bound(n, d, 2T)[2T]
+ * or mjx_sa_csr_ball_bound(.., 2T)[2T]; both serve radius <= 6, so T <= 3) and
+ * the list of min(n, cap2T) entries joins the job's LDS:
+ *   mjx_quench_exchange_jobs_lds(n, T, caps, cap2T) =
+ *     mjx_quench_jobs_lds(n, T, caps) + 4 * min(n, cap2T), rounded up to 16;
+ *   -1 as mjx_quench_jobs_lds, for T > 3, cap2T < 1, or past the same 64 KiB.
+ * rank_work: device int32 [R*K*n], workspace (a job's inverse order; need not
+ * be initialised).  max_passes >= 1.  Further outputs, device arrays [R*K]:
+ * plus_quench (+1 spins after the quench pass), exchanges, passes (int64),
+ * converged (bytes 0 / 1).  flag: bits 0 and 1 as above (a candidate list past
+ * cap2T counts as bit 0), bit 2 = a flip that restores the state after an add
+ * without two drops did not commit (a bug, never an input error).  stats: NULL,
+ * or device int64 [R*K][4] = adds tried, candidate drops tried, and the device's
+ * constant-rate clock ticks of the quench phase and of the passes.
+ * MJX_EINVAL: as mjx_quench_jobs_*, T > 3, max_passes < 1, cap2T < 1, a NULL
+ * pointer other than stats.  No allocation, no host synchronisation.
+ */
+int64_t mjx_quench_exchange_jobs_lds(int64_t n, int T, const int64_t* caps, int64_t cap2T);
+int mjx_quench_exchange_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t graph_stride, int64_t R, int64_t K,
+                                 int p, int c, const int64_t* caps, int64_t cap2T, int max_passes,
+                                 const uint64_t* s_np, const int32_t* order, int64_t order_stride_r,
+                                 int32_t* rank_work, uint64_t* out_np, int64_t* flipped, int64_t* plus,
+                                 int64_t* plus_quench, int64_t* exchanges, int64_t* passes, uint8_t* converged,
+                                 uint8_t* consensus, int32_t* flag, int64_t* stats, void* stream);
+int mjx_quench_exchange_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int64_t K, int p,
+                                 int c, const int64_t* caps, int64_t cap2T, int max_passes, const uint64_t* s_np,
+                                 const int32_t* order, int64_t order_stride_r, int32_t* rank_work, uint64_t* out_np,
+                                 int64_t* flipped, int64_t* plus, int64_t* plus_quench, int64_t* exchanges,
+                                 int64_t* passes, uint8_t* converged, uint8_t* consensus, int32_t* flag,
+                                 int64_t* stats, void* stream);
+
 /* ---- exact consensus census of a small graph ------------------------------- */
 /*
  * Ground truth by exhaustive enumeration: every start configuration of a graph

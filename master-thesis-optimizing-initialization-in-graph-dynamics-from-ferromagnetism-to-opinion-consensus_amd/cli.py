@@ -28,7 +28,10 @@ and write its np.savez keys.
         (with ``--order-seed``): best of K orders per replica, all (replica,
         order) jobs in one call (quench.quench_restarts), a graph per replica
         for ``graphs`` files; the same keys for the best restart plus
-        mag_restarts (R, K) and best.  ``--schedule regions [--window K]``:
+        mag_restarts (R, K) and best.  ``--exchange [--max-passes P]`` (with
+        ``--restarts K``): the (1, 2) exchange descent behind every job's pass
+        (quench.quench_exchange); adds mag_quench, exchanges, passes, converged
+        (R, K).  ``--schedule regions [--window K]``:
         the single pass in rounds (same output; quench.quench's schedule)
   census  no reference script: the exact consensus census (census.census) of
         one small random regular or Erdos-Renyi graph (n <= 48, isolated nodes
@@ -121,6 +124,12 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--window K (K >= 1) belongs to --schedule regions")
             if a.schedule == "regions" and a.restarts >= 1:
                 self.error("--schedule regions is a schedule of the single pass: not with --restarts")
+            if a.exchange and a.restarts < 1:
+                self.error("--exchange runs behind the jobs of --restarts K --order-seed S (K >= 1)")
+            if a.exchange and a.schedule == "regions":
+                self.error("--schedule regions is a schedule of the single pass: not with --exchange")
+            if a.max_passes is not None and (not a.exchange or a.max_passes < 1):
+                self.error("--max-passes P (P >= 1) belongs to --exchange")
         return a
 
 
@@ -183,6 +192,12 @@ def build_parser():
                     help="K >= 1: best of K orders per replica in one call (quench.quench_restarts), job (r, k) "
                          "walking np.random.default_rng([S, r, k]).permutation(n) with S = --order-seed (required); "
                          "0: one pass as above")
+    qu.add_argument("--exchange", action="store_true",
+                    help="with --restarts K: leave every job's local minimum downwards by (1, 2) exchanges, one -1 "
+                         "spin to +1 and two +1 spins dropped (quench.quench_exchange); p + c - 1 <= 3")
+    qu.add_argument("--max-passes", type=int, default=None,
+                    help="--exchange: passes over the order at most (default 8); they end with the first that "
+                         "commits nothing")
     qu.add_argument("--schedule", choices=("sequential", "regions"), default="sequential",
                     help="of the single pass (--restarts 0): regions commits candidates whose balls do not meet in "
                          "the same round; same output, faster on large graphs")
@@ -378,9 +393,15 @@ def run_quench(a):
     if a.restarts >= 1:
         # best of K orders per replica, every (replica, order) a job of one call; SA / HPR files: the
         # (R, n, d) stack, a graph per replica
-        from .quench import quench_restarts
+        from .quench import quench_exchange, quench_restarts
         g = res["graphs"].astype(np.int32) if "graphs" in res else Graph.csr(res["row_ptr"], res["col"])
-        qr = quench_restarts(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed)
+        if a.exchange:
+            qr = quench_exchange(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed,
+                                 max_passes=8 if a.max_passes is None else a.max_passes)
+            for key in ("mag_quench", "exchanges", "passes", "converged"):
+                res[key] = qr[key]
+        else:
+            qr = quench_restarts(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed)
         q = {"conf": qr["conf_best"], "mag": qr["mag_best"], "consensus": qr["consensus"],
              "flipped": qr["flipped"][np.arange(S.shape[0]), qr["best"]]}      # of the restart that is kept
         res["mag_restarts"], res["best"] = qr["mag"], qr["best"]

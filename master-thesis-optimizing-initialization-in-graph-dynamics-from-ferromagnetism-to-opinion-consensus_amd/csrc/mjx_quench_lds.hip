@@ -31,6 +31,8 @@ constexpr int QJ_MAXT = 6;
 constexpr int64_t kQjLdsMax = 64 * 1024;      // the ceiling of mjx_quench.hip: no dynamic-LDS opt-in
 constexpr int QJ_OVERFLOW = 1;                // flag bits of a job
 constexpr int QJ_BAD_INDEX = 2;
+constexpr int QJ_RESTORE = 4;                 // exchange only: a restoring flip did not commit
+constexpr int QX_MAXT = 3;                    // exchange only: the candidate list is a ball of radius 2T <= 6
 
 struct QjPlan {
     int T;
@@ -59,8 +61,10 @@ __device__ __forceinline__ bool qj_new(const Adj& A, const uint32_t* Lp, int v, 
 // Try the flip of node i (L_0[i] = +1, L_T all +1).  Wave-uniform; returns 1
 // when the flip is committed, 0 when it is refused (the levels are as before),
 // -QJ_OVERFLOW / -QJ_BAD_INDEX when the job has to stop (the levels are void).
-template <class Adj>
-__device__ int qj_try(const Adj& A, const QjPlan& P, uint32_t* lds, int n, int i) {
+// Counts: a committed flip leaves the sizes of its lists in cnt_out[0 .. QJ_MAXT]
+// (list l = the nodes whose level-l value the flip changed; 0 from the level it died out at).
+template <class Adj, bool Counts = false>
+__device__ int qj_try(const Adj& A, const QjPlan& P, uint32_t* lds, int n, int i, int* cnt_out = nullptr) {
     const int lane = threadIdx.x;
     const u64 below = (1ull << lane) - 1;
     const int T = P.T, W32 = P.W32;
@@ -145,7 +149,13 @@ __device__ int qj_try(const Adj& A, const QjPlan& P, uint32_t* lds, int n, int i
         __syncthreads();
     }
     if (err) return -err;
-    if (!refuse) return 1;
+    if (!refuse) {
+        if constexpr (Counts) {
+#pragma unroll
+            for (int l = 0; l <= QJ_MAXT; ++l) cnt_out[l] = cnt[l];
+        }
+        return 1;
+    }
 #pragma unroll
     for (int l = 0; l < QJ_MAXT; ++l) {                      // level T is never turned
         if (l > applied) break;
@@ -157,31 +167,25 @@ __device__ int qj_try(const Adj& A, const QjPlan& P, uint32_t* lds, int n, int i
     return 0;
 }
 
+// valid bits of bitmap word w
+__device__ __forceinline__ uint32_t qj_valid(int n, int w) {
+    const int left = n - w * 32;
+    return left >= 32 ? ~0u : (left <= 0 ? 0u : ((1u << left) - 1u));
+}
+
+// Steps 1-4 of a job: the start into L_0, the T sweeps, the consensus test and the
+// walk over `ord`.  s_np / r: the starts and the job's row of them.  Returns the job's
+// flag (0, QJ_OVERFLOW or QJ_BAD_INDEX).
 template <class Adj>
-__global__ void __launch_bounds__(64) k_quench_jobs(Adj A0, QjPlan P, int n, int64_t graph_stride, int K,
-                                                    const uint32_t* __restrict__ s_np,
-                                                    const int32_t* __restrict__ order, int64_t order_stride_r,
-                                                    uint32_t* __restrict__ out_np, long long* __restrict__ flipped,
-                                                    long long* __restrict__ plus, uint8_t* __restrict__ consensus,
-                                                    int32_t* __restrict__ flag) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t qj_lds[];
+__device__ __forceinline__ int qj_quench_phase(const Adj& A, const QjPlan& P, int n, const uint32_t* __restrict__ s_np,
+                                               int64_t r, const int32_t* __restrict__ ord, uint32_t* qj_lds,
+                                               bool& cons, long long& nflip) {
     const int lane = threadIdx.x;
     const int T = P.T, W32 = P.W32;
-    const int64_t job = blockIdx.x;
-    const int64_t r = job / K;
-    const int k = (int)(job - r * K);
-    const Adj A = A0.at(r * graph_stride);
-    const int32_t* ord = order + r * order_stride_r + (int64_t)k * n;
     uint32_t* mark = qj_lds + (T + 1) * W32;
-
-    // valid bits of bitmap word w
-    auto valid = [&](int w) -> uint32_t {
-        const int left = n - w * 32;
-        return left >= 32 ? ~0u : (left <= 0 ? 0u : ((1u << left) - 1u));
-    };
     // 1. the start (padding bits 0 whatever the caller left there), marks cleared
     for (int w = lane; w < W32; w += 64) {
-        qj_lds[w] = s_np[r * W32 + w] & valid(w);
+        qj_lds[w] = s_np[r * W32 + w] & qj_valid(n, w);
         mark[w] = 0;
     }
     __syncthreads();
@@ -202,11 +206,11 @@ __global__ void __launch_bounds__(64) k_quench_jobs(Adj A0, QjPlan P, int n, int
     }
     // 3. consensus: every valid bit of L_T set
     bool all = true;
-    for (int w = lane; w < W32; w += 64) all = all && qj_lds[T * W32 + w] == valid(w);
-    const bool cons = __ballot(!all) == 0;
+    for (int w = lane; w < W32; w += 64) all = all && qj_lds[T * W32 + w] == qj_valid(n, w);
+    cons = __ballot(!all) == 0;
     // 4. the walk.  Node i is visited once and only its own flip turns bit i of L_0, so the
     //    +1 test of 64 order entries at a time holds when their turn comes.
-    long long nflip = 0;
+    nflip = 0;
     int err = 0;
     if (cons && T > 0) {
         for (int base = 0; base < n && !err; base += 64) {
@@ -231,7 +235,13 @@ __global__ void __launch_bounds__(64) k_quench_jobs(Adj A0, QjPlan P, int n, int
             }
         }
     }
-    // 5. the result; a stopped job (flag != 0) writes words of no meaning, all in bounds
+    return err;
+}
+
+// Step 5, the result: L_0 to the job's row of out_np; returns its +1 spins.  A stopped
+// job (flag != 0) writes words of no meaning, all in bounds.
+__device__ __forceinline__ int qj_store(const uint32_t* qj_lds, int W32, uint32_t* __restrict__ out_np, int64_t job) {
+    const int lane = threadIdx.x;
     int ones = 0;
     for (int w = lane; w < W32; w += 64) {
         const uint32_t x = qj_lds[w];
@@ -239,11 +249,232 @@ __global__ void __launch_bounds__(64) k_quench_jobs(Adj A0, QjPlan P, int n, int
         ones += __popc(x);
     }
     for (int off = 32; off; off >>= 1) ones += __shfl_xor(ones, off);
-    if (lane == 0) {
+    return ones;
+}
+
+template <class Adj>
+__global__ void __launch_bounds__(64) k_quench_jobs(Adj A0, QjPlan P, int n, int64_t graph_stride, int K,
+                                                    const uint32_t* __restrict__ s_np,
+                                                    const int32_t* __restrict__ order, int64_t order_stride_r,
+                                                    uint32_t* __restrict__ out_np, long long* __restrict__ flipped,
+                                                    long long* __restrict__ plus, uint8_t* __restrict__ consensus,
+                                                    int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t qj_lds[];
+    const int64_t job = blockIdx.x;
+    const int64_t r = job / K;
+    const int k = (int)(job - r * K);
+    const Adj A = A0.at(r * graph_stride);
+    const int32_t* ord = order + r * order_stride_r + (int64_t)k * n;
+    bool cons;
+    long long nflip;
+    const int err = qj_quench_phase(A, P, n, s_np, r, ord, qj_lds, cons, nflip);
+    const int ones = qj_store(qj_lds, P.W32, out_np, job);
+    if (threadIdx.x == 0) {
         flipped[job] = nflip;
         plus[job] = ones;
         flag[job] = err;
         if (k == 0) consensus[r] = cons ? 1 : 0;
+    }
+}
+
+// ---- the (1, 2) exchange descent behind the quench pass (definitions: include/mjx.h) ----
+__device__ __forceinline__ int qx_wave_min(int x) { return -qn_wave_max(-x); }
+
+// One offer round of the candidate search: lanes with `valid` offer node x; an offer
+// without a mark gets one and is appended to xl[0 .. qn).  Returns false, with nothing
+// appended, when the list would outgrow cap.  No barrier.
+__device__ __forceinline__ bool qx_offer(uint32_t* mark, uint32_t* xl, int& qn, int cap, uint32_t x, bool valid) {
+    const u64 below = (1ull << threadIdx.x) - 1;
+    bool fresh = false;
+    if (valid) {
+        const uint32_t b = 1u << (x & 31);
+        fresh = !(atomicOr(&mark[x >> 5], b) & b);
+    }
+    const u64 mask = __ballot(fresh);
+    const int total = qn + __popcll(mask);
+    if (total > cap) return false;
+    if (fresh) xl[qn + __popcll(mask & below)] = x;
+    qn = total;
+    return true;
+}
+
+// Add node j (L_0[j] = -1, L_T all +1, L_0 a single-flip local minimum) and drop what
+// the add allows.  The candidates are the +1 nodes within t + 2 hops of a node whose
+// level-t value the add changed (t < T), tried in ascending rank = position in `ord`
+// (xl holds the ranks: ord[rank] is the node).  Wave-uniform; returns 1 when two or more
+// nodes dropped (the exchange stays), 0 when the levels are as before, -flag when the
+// job has to stop.
+template <class Adj>
+__device__ int qx_add(const Adj& A, const QjPlan& P, uint32_t* lds, uint32_t* xl, int xcap, int n, int j,
+                      const int32_t* __restrict__ ord, const int32_t* rank, long long& ntry) {
+    const int lane = threadIdx.x;
+    const u64 below = (1ull << lane) - 1;
+    const int T = P.T, W32 = P.W32;
+    uint32_t* mark = lds + (T + 1) * W32;
+    const uint32_t* lists = mark + W32;
+    int cnt[QJ_MAXT + 1];
+    int res = qj_try<Adj, true>(A, P, lds, n, j, cnt);
+    if (res != 1) return res < 0 ? res : -QJ_RESTORE;        // an add changes nothing at level T
+    // the search, by remaining hops h = T + 1 .. 1: the frontier xl[fs .. qn) is what the
+    // frontier of h + 1 reached plus the changed nodes of level h - 2; a node's first
+    // visit is the one with the most hops left, so a mark per node is enough
+    int qn = 0, fs = 0, err = 0;
+#pragma unroll
+    for (int t = QX_MAXT - 1; t >= -1; --t) {
+        if (t >= T || err) continue;
+        if (t >= 0) {
+            const uint32_t* src = lists + P.off[t];
+            for (int base = 0; base < cnt[t] && !err; base += 64) {
+                const bool have = base + lane < cnt[t];
+                if (!qx_offer(mark, xl, qn, xcap, have ? src[base + lane] : 0u, have)) err = QJ_OVERFLOW;
+            }
+        }
+        __syncthreads();
+        const int fe = qn;
+        for (int base = fs; base < fe && !err; base += 64) {
+            const bool have = base + lane < fe;
+            const int v = have ? (int)xl[base + lane] : 0;
+            const int dg = have ? A.deg(v) : 0;
+            const int32_t* row = have ? A.row(v) : nullptr;
+            const int longest = qn_wave_max(dg);
+            for (int e = 0; e < longest && !err; ++e) {
+                const bool in = e < dg;
+                const uint32_t x = in ? (uint32_t)row[e] : 0u;
+                const bool bad = in && x >= (uint32_t)n;
+                if (__ballot(bad)) err = QJ_BAD_INDEX;
+                else if (!qx_offer(mark, xl, qn, xcap, x, in)) err = QJ_OVERFLOW;
+            }
+        }
+        fs = fe;
+    }
+    if (err) return -err;
+    __syncthreads();
+    // marks cleared; the +1 nodes other than j stay, as ranks
+    int nk = 0;
+    for (int base = 0; base < qn; base += 64) {
+        const bool has = base + lane < qn;
+        const int v = has ? (int)xl[base + lane] : 0;
+        bool keep = false;
+        if (has) {
+            mark[v >> 5] = 0;
+            keep = v != j && qj_bit(lds, v);
+        }
+        const int rk = keep ? rank[v] : 0;
+        const u64 mask = __ballot(keep);                     // every lane has read its entry here
+        if (keep) xl[nk + __popcll(mask & below)] = (uint32_t)rk;
+        nk += __popcll(mask);
+    }
+    __syncthreads();
+    int dropped = 0, first = -1, prev = -1;
+    for (int it = 0; it < nk && dropped + (nk - it) >= 2; ++it) {      // one drop is no exchange
+        int best = INT32_MAX;
+        for (int q = lane; q < nk; q += 64) {
+            const int rk = (int)xl[q];
+            if (rk > prev && rk < best) best = rk;
+        }
+        best = qx_wave_min(best);
+        if (best >= n) return -QJ_BAD_INDEX;                 // ranks of an order that is no permutation
+        prev = best;
+        const int a = ord[best];
+        if ((uint32_t)a >= (uint32_t)n || a == j || !qj_bit(lds, a)) return -QJ_BAD_INDEX;
+        res = qj_try(A, P, lds, n, a);
+        ++ntry;
+        if (res < 0) return res;
+        if (res && !dropped) first = a;
+        dropped += res;
+    }
+    if (dropped >= 2) return 1;
+    // as before: the single drop back, then j out; both commit by construction
+    if (dropped == 1) {
+        res = qj_try(A, P, lds, n, first);
+        if (res != 1) return res < 0 ? res : -QJ_RESTORE;
+    }
+    res = qj_try(A, P, lds, n, j);
+    if (res != 1) return res < 0 ? res : -QJ_RESTORE;
+    return 0;
+}
+
+// stats (may be NULL): int64 [jobs][4] = adds, candidate tries, device clock ticks of
+// the quench phase and of the exchange phase
+template <class Adj>
+__global__ void __launch_bounds__(64)
+k_quench_exchange_jobs(Adj A0, QjPlan P, int xcap, int xoff, int n, int64_t graph_stride, int K, int max_passes,
+                       const uint32_t* __restrict__ s_np, const int32_t* __restrict__ order, int64_t order_stride_r,
+                       int32_t* rank_work, uint32_t* __restrict__ out_np, long long* __restrict__ flipped,
+                       long long* __restrict__ plus, long long* __restrict__ plus_quench,
+                       long long* __restrict__ exchanges, long long* __restrict__ passes,
+                       uint8_t* __restrict__ converged, uint8_t* __restrict__ consensus, int32_t* __restrict__ flag,
+                       long long* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t qj_lds[];
+    const int lane = threadIdx.x;
+    const int64_t job = blockIdx.x;
+    const int64_t r = job / K;
+    const int k = (int)(job - r * K);
+    const Adj A = A0.at(r * graph_stride);
+    const int32_t* ord = order + r * order_stride_r + (int64_t)k * n;
+    const long long t0 = (long long)wall_clock64();
+    bool cons;
+    long long nflip;
+    int err = qj_quench_phase(A, P, n, s_np, r, ord, qj_lds, cons, nflip);
+    int ones_q = 0;
+    for (int w = lane; w < P.W32; w += 64) ones_q += __popc(qj_lds[w]);
+    for (int off = 32; off; off >>= 1) ones_q += __shfl_xor(ones_q, off);
+    const long long t1 = (long long)wall_clock64();
+    // 5. the passes.  A committed exchange turns other nodes to -1, so the -1 test of the
+    //    64 order entries is taken again after it; the order was checked by the walk.
+    long long nex = 0, nadd = 0, ntry = 0;
+    int npass = cons && P.T == 0 ? 1 : 0;                    // T = 0: all +1, a pass without an add
+    bool conv = true;
+    if (cons && P.T > 0 && !err) {
+        conv = false;
+        int32_t* rank = rank_work + job * n;
+        for (int q = lane; q < n; q += 64) rank[ord[q]] = q;
+        __syncthreads();
+        uint32_t* xl = qj_lds + xoff;
+        for (int ps = 1; ps <= max_passes && !err && !conv; ++ps) {
+            bool moved = false;
+            for (int base = 0; base < n && !err; base += 64) {
+                const int q = base + lane;
+                const int oi = q < n ? ord[q] : 0;
+                u64 todo = __ballot(q < n && !qj_bit(qj_lds, oi));
+                while (todo) {
+                    const int m = __ffsll((long long)todo) - 1;
+                    const int j = __builtin_amdgcn_readlane(oi, m);
+                    const int res = qx_add(A, P, qj_lds, xl, xcap, n, j, ord, rank, ntry);
+                    ++nadd;
+                    if (res < 0) {
+                        err = -res;
+                        break;
+                    }
+                    if (res) {
+                        ++nex;
+                        moved = true;
+                        todo = __ballot(q < n && !qj_bit(qj_lds, oi)) & ~((2ull << m) - 1);
+                    } else {
+                        todo &= todo - 1;
+                    }
+                }
+            }
+            npass = ps;
+            conv = !err && !moved;
+        }
+    }
+    const int ones = qj_store(qj_lds, P.W32, out_np, job);
+    if (lane == 0) {
+        flipped[job] = nflip;
+        plus[job] = ones;
+        plus_quench[job] = ones_q;
+        exchanges[job] = nex;
+        passes[job] = npass;
+        converged[job] = conv ? 1 : 0;
+        flag[job] = err;
+        if (k == 0) consensus[r] = cons ? 1 : 0;
+        if (stats) {
+            stats[job * 4 + 0] = nadd;
+            stats[job * 4 + 1] = ntry;
+            stats[job * 4 + 2] = t1 - t0;
+            stats[job * 4 + 3] = (long long)wall_clock64() - t1;
+        }
     }
 }
 
@@ -267,16 +498,50 @@ int qj_plan(int64_t n, int T, const int64_t* caps, QjPlan& P) {
     return MJX_OK;
 }
 
+// what the exchange entry points take on top of the quench ones
+struct QxArgs {
+    int64_t cap2T;
+    int max_passes;
+    int32_t* rank_work;
+    int64_t *plus_quench, *exchanges, *passes;
+    uint8_t* converged;
+    int64_t* stats;                // may be NULL
+};
+
+// the exchange's LDS: the quench job's, then the candidate list of min(n, cap2T) entries
+int qx_plan(int64_t n, int T, const int64_t* caps, int64_t cap2T, QjPlan& P, int& xcap, int64_t& bytes) {
+    if (T > QX_MAXT || cap2T < 1) return MJX_EINVAL;
+    if (int rc = qj_plan(n, T, caps, P)) return rc;
+    xcap = (int)std::min<int64_t>(n, cap2T);
+    bytes = (P.bytes + 4 * (int64_t)xcap + 15) / 16 * 16;
+    return bytes > kQjLdsMax ? MJX_EINVAL : MJX_OK;
+}
+
 template <class Adj>
 int quench_jobs_run(Adj A, int64_t n, int64_t graph_stride, int64_t R, int64_t K, int p, int c, const int64_t* caps,
                     const uint64_t* s_np, const int32_t* order, int64_t order_stride_r, uint64_t* out_np,
-                    int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag, void* stream) {
+                    int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag, void* stream,
+                    const QxArgs* X = nullptr) {
     const int T = p + c - 1;
     if (p < 0 || c < 0 || R < 1 || K < 1 || K > (int64_t)INT32_MAX || R * K > (int64_t)INT32_MAX || !s_np || !order ||
         !out_np || !flipped || !plus || !consensus || !flag)
         return MJX_EINVAL;
     if (graph_stride < 0 || (order_stride_r != 0 && order_stride_r != K * n)) return MJX_EINVAL;
     QjPlan P;
+    if (X) {
+        if (X->max_passes < 1 || !X->rank_work || !X->plus_quench || !X->exchanges || !X->passes || !X->converged)
+            return MJX_EINVAL;
+        int xcap;
+        int64_t bytes;
+        if (int rc = qx_plan(n, T, caps, X->cap2T, P, xcap, bytes)) return rc;
+        k_quench_exchange_jobs<Adj><<<(unsigned)(R * K), 64, (size_t)bytes, as_stream(stream)>>>(
+            A, P, xcap, (int)(P.bytes / 4), (int)n, graph_stride, (int)K, X->max_passes, (const uint32_t*)s_np, order,
+            order_stride_r, X->rank_work, (uint32_t*)out_np, (long long*)flipped, (long long*)plus,
+            (long long*)X->plus_quench, (long long*)X->exchanges, (long long*)X->passes, X->converged, consensus, flag,
+            (long long*)X->stats);
+        MJX_LAUNCH_CHECK("k_quench_exchange_jobs");
+        return MJX_OK;
+    }
     if (int rc = qj_plan(n, T, caps, P)) return rc;
     k_quench_jobs<Adj><<<(unsigned)(R * K), 64, (size_t)P.bytes, as_stream(stream)>>>(
         A, P, (int)n, graph_stride, (int)K, (const uint32_t*)s_np, order, order_stride_r, (uint32_t*)out_np,
@@ -311,4 +576,37 @@ extern "C" int mjx_quench_jobs_csr(const int64_t* row_ptr, const int32_t* col, i
     if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
     return quench_jobs_run(AdjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
                            plus, consensus, flag, stream);
+}
+
+extern "C" int64_t mjx_quench_exchange_jobs_lds(int64_t n, int T, const int64_t* caps, int64_t cap2T) {
+    QjPlan P;
+    int xcap;
+    int64_t bytes;
+    return qx_plan(n, T, caps, cap2T, P, xcap, bytes) ? -1 : bytes;
+}
+
+extern "C" int mjx_quench_exchange_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t graph_stride, int64_t R,
+                                            int64_t K, int p, int c, const int64_t* caps, int64_t cap2T,
+                                            int max_passes, const uint64_t* s_np, const int32_t* order,
+                                            int64_t order_stride_r, int32_t* rank_work, uint64_t* out_np,
+                                            int64_t* flipped, int64_t* plus, int64_t* plus_quench, int64_t* exchanges,
+                                            int64_t* passes, uint8_t* converged, uint8_t* consensus, int32_t* flag,
+                                            int64_t* stats, void* stream) {
+    if (!adj_ell_ok(adj, d) || (graph_stride != 0 && graph_stride != n * d)) return MJX_EINVAL;
+    const QxArgs X{cap2T, max_passes, rank_work, plus_quench, exchanges, passes, converged, stats};
+    return quench_jobs_run(AdjEll{adj, d}, n, graph_stride, R, K, p, c, caps, s_np, order, order_stride_r, out_np,
+                           flipped, plus, consensus, flag, stream, &X);
+}
+
+extern "C" int mjx_quench_exchange_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int64_t K,
+                                            int p, int c, const int64_t* caps, int64_t cap2T, int max_passes,
+                                            const uint64_t* s_np, const int32_t* order, int64_t order_stride_r,
+                                            int32_t* rank_work, uint64_t* out_np, int64_t* flipped, int64_t* plus,
+                                            int64_t* plus_quench, int64_t* exchanges, int64_t* passes,
+                                            uint8_t* converged, uint8_t* consensus, int32_t* flag, int64_t* stats,
+                                            void* stream) {
+    if (!adj_csr_ok(row_ptr)) return MJX_EINVAL;
+    const QxArgs X{cap2T, max_passes, rank_work, plus_quench, exchanges, passes, converged, stats};
+    return quench_jobs_run(AdjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
+                           plus, consensus, flag, stream, &X);
 }

@@ -26,6 +26,12 @@ R starts x K orders as R K independent jobs in one call
 node-packed in LDS), with an order per job and, for an (R, n, d) stack, a graph
 per start, and returns the best of the K results per start.
 
+Every one of these ends in a single-flip local minimum.  ``quench_exchange``
+runs the same jobs and then leaves that minimum downwards by (1, 2) exchanges:
+one -1 spin becomes +1, two +1 spins near it are dropped, in passes over the
+job's order until a pass commits nothing (k_quench_exchange_jobs in the same
+unit; p + c - 1 <= 3).
+
 Not covered: packed input to ``quench_restarts``, a CSR graph per start,
 several devices.  There is no CPU fallback.
 """
@@ -475,31 +481,149 @@ def _host_shapes(graph, s):
     return stack, n, R
 
 
-def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t):
+def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t, exchange=None, what="quench_restarts"):
     """The device call: R x K jobs -> (out_np int64 (R K, ceil(n/64)), flipped int64 [R K], plus int64 [R K],
     consensus uint8 [R]).  g: the shared graph, or any graph of ``adj_stack`` (device int32 (R, n, d): a graph
-    per start); s_np int64 (R, ceil(n/64)); order_t device int32 (1 or R, K, n)."""
+    per start); s_np int64 (R, ceil(n/64)); order_t device int32 (1 or R, K, n).  ``exchange`` = (cap2T,
+    max_passes, "with stats"): the exchange descent behind the pass (mjx_quench_exchange_jobs_*); a fifth
+    entry of the result then holds plus_quench, exchanges, passes int64 [R K], converged uint8 [R K] and
+    stats int64 (R K, 4) or None."""
     n, dev, st = g.n, s_np.device, _device.stream_handle()
     Wn = (n + 63) // 64
-    out_np = torch.empty((R * K, Wn), dtype=torch.int64, device=dev)
-    flipped = torch.empty(R * K, dtype=torch.int64, device=dev)
-    plus = torch.empty(R * K, dtype=torch.int64, device=dev)
-    consensus = torch.empty(R, dtype=torch.uint8, device=dev)
-    flag = torch.empty(R * K, dtype=torch.int32, device=dev)
-    tail = (R, K, p, c, caps, _device.ptr(s_np), _device.ptr(order_t), K * n if order_t.shape[0] > 1 else 0,
-            _device.ptr(out_np), _device.ptr(flipped), _device.ptr(plus), _device.ptr(consensus), _device.ptr(flag), st)
+
+    def new(dtype, *shape):
+        return torch.empty(shape or (R * K,), dtype=dtype, device=dev)
+
+    out_np, flipped, plus = new(torch.int64, R * K, Wn), new(torch.int64), new(torch.int64)
+    consensus, flag = new(torch.uint8, R), new(torch.int32)
+    jobs = (R, K, p, c, caps)
+    starts = (_device.ptr(s_np), _device.ptr(order_t), K * n if order_t.shape[0] > 1 else 0)
+    outs = (_device.ptr(out_np), _device.ptr(flipped), _device.ptr(plus))
+    ends = (_device.ptr(consensus), _device.ptr(flag))
+    if exchange is None:
+        entry, tail, more = "mjx_quench_jobs", (*jobs, *starts, *outs, *ends, st), None
+    else:
+        cap2T, max_passes, with_stats = exchange
+        rank = new(torch.int32, R * K * n)
+        more = {"plus_quench": new(torch.int64), "exchanges": new(torch.int64), "passes": new(torch.int64),
+                "converged": new(torch.uint8), "stats": new(torch.int64, R * K, 4) if with_stats else None}
+        entry = "mjx_quench_exchange_jobs"
+        tail = (*jobs, cap2T, max_passes, *starts, _device.ptr(rank), *outs, _device.ptr(more["plus_quench"]),
+                _device.ptr(more["exchanges"]), _device.ptr(more["passes"]), _device.ptr(more["converged"]), *ends,
+                _device.ptr(more["stats"]), st)
     if g.kind == "ell":
         adj = g.adj if adj_stack is None else adj_stack
-        _lib.call("mjx_quench_jobs_ell", _device.ptr(adj) if g.d else None, n, g.d,
-                  0 if adj_stack is None else n * g.d, *tail)
+        _lib.call(entry + "_ell", _device.ptr(adj) if g.d else None, n, g.d, 0 if adj_stack is None else n * g.d, *tail)
     else:
-        _lib.call("mjx_quench_jobs_csr", _device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n, *tail)
+        _lib.call(entry + "_csr", _device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n, *tail)
     flags = int(flag.max().item())
     if flags & 1:
-        raise _lib.MjxError("quench_restarts: a light-cone list outgrew the ball bound of the graph")
+        raise _lib.MjxError(f"{what}: a light-cone list outgrew the ball bound of the graph")
+    if flags & 2:
+        raise _lib.MjxError(f"{what}: an order or adjacency entry lies outside 0..n-1")
     if flags:
-        raise _lib.MjxError("quench_restarts: an order or adjacency entry lies outside 0..n-1")
-    return out_np, flipped, plus, consensus
+        raise _lib.MjxError(f"{what}: a flip that restores the state did not commit (a bug in the kernel)")
+    res = (out_np, flipped, plus, consensus)
+    return res if exchange is None else res + (more,)
+
+
+EXCHANGE_T_MAX = 3          # the candidates of an add lie in a ball of radius 2T, and the ball bounds serve 6
+
+
+def _quench_jobs(what, graph, s, p, c, restarts, orders, seed, keep_all, kernel, validate, exchange=False,
+                 max_passes=None):
+    """``quench_restarts`` and ``quench_exchange`` (``exchange``, with its ``max_passes``): the checks, the
+    device call and the result dict they share."""
+    p, c, T = _steps(p, c)
+    if kernel:
+        raise ValueError(f"unknown kernel options {sorted(dict(kernel))}")
+    if exchange:
+        if T > EXCHANGE_T_MAX:
+            raise ValueError(f"{what}: need p + c - 1 <= {EXCHANGE_T_MAX} (the candidates of an add fill a ball of "
+                             f"radius 2 (p + c - 1)), got p = {p}, c = {c}")
+        if not isinstance(max_passes, (int, np.integer)) or isinstance(max_passes, bool) or max_passes < 1:
+            raise ValueError(f"max_passes must be an integer >= 1, got {max_passes!r}")
+        max_passes = int(max_passes)
+    stack, n, R = _host_shapes(graph, s)
+    K = int(restarts)
+    orders = _check_orders(orders, seed, K, R, n)
+    lib = _lib.load()
+
+    def lds_of(caps, caps2):
+        """LDS bytes of a job; refuses a shape that does not fit."""
+        lds = int(lib.mjx_quench_exchange_jobs_lds(n, T, caps, caps2[2 * T]) if exchange else
+                  lib.mjx_quench_jobs_lds(n, T, caps))
+        if lds < 0:
+            raise ValueError(f"{what}: a job of n = {n}, p + c - 1 = {T} (ball bound {list(caps)}) does not fit "
+                             "the workgroup's LDS; quench is the path for this shape")
+        return lds
+
+    def ell_caps(d, radius):
+        out = (_lib.c_i64 * (radius + 1))()
+        _lib.call("mjx_ell_ball_bound", n, d, radius, out)
+        return out
+
+    d_host = graph.d if isinstance(graph, Graph) and graph.kind == "ell" else \
+        None if isinstance(graph, Graph) else int((graph.shape if hasattr(graph, "shape") else np.shape(graph))[-1])
+    if d_host is not None and 0 <= d_host <= 255:
+        # a neighbour array: the budget is a function of (n, d), known before anything reaches the device
+        lds_of(ell_caps(d_host, T), ell_caps(d_host, 2 * T) if exchange else None)
+    if stack:
+        adj = graph.cpu().numpy() if isinstance(graph, torch.Tensor) else np.asarray(graph)
+        if not np.issubdtype(adj.dtype, np.integer):
+            raise ValueError("the (R, n, d) graph stack must be an integer array")
+        if adj.size and (adj.min() < 0 or adj.max() >= n):
+            raise ValueError("adjacency index out of range")
+        d = int(adj.shape[2])
+        adj_t = _device.to_device(adj.astype(np.int32, copy=False))
+        graphs = [Graph("ell", n, d=d, adj=adj_t[r]) for r in range(R)]
+        g = graphs[0]
+    else:
+        g = as_graph(graph)
+        graphs = [g]
+    if validate:
+        for gr in graphs:
+            _check_symmetric(gr)
+    caps = _caps(g, T)                      # ELL: a function of (n, d) alone, the same for every graph of a stack
+    caps2 = _caps(g, 2 * T) if exchange else None
+    lds_of(caps, caps2)
+    t, vector = _spins_2d(s)
+    dev, st, Wn = t.device, _device.stream_handle(), (n + 63) // 64
+    s_np = torch.empty((R, Wn), dtype=torch.int64, device=dev)
+    code, step = _device.dtype_code(t), n * t.element_size()
+    for r in range(R):
+        _lib.call("mjx_pack_np", t.data_ptr() + r * step, code, n, s_np.data_ptr() + r * Wn * 8, st)
+    order_t = _device.to_device(orders)
+    out_np, flipped, plus, consensus, *more = _run_jobs(
+        g, adj_t if stack else None, R, K, p, c, caps, s_np, order_t,
+        (int(caps2[2 * T]), max_passes, False) if exchange else None, what)
+    sums = 2 * plus.cpu().numpy().reshape(R, K) - n
+    best = pick_best(sums)
+    # sum(s) / n as numpy divides two integers, as quench does
+    mag = sums / n
+    mag_best = mag[np.arange(R), best]
+    state_best = out_np.view(R, K, Wn)[torch.arange(R, device=dev), torch.from_numpy(best).to(dev)].contiguous()
+
+    def rows(bits, dtype):
+        conf = torch.empty((bits.shape[0], n), dtype=dtype, device=dev)
+        dc, row = _device.dtype_code(conf), n * conf.element_size()
+        for j in range(bits.shape[0]):
+            _lib.call("mjx_unpack_np", bits.data_ptr() + j * Wn * 8, n, conf.data_ptr() + j * row, dc, st)
+        return conf
+
+    conf_best = _conf_like(rows(state_best, t.dtype), s, vector)
+    out = {"mag": _like(torch.from_numpy(mag), s), "flipped": _like(flipped.view(R, K), s),
+           "consensus": _like(consensus.to(torch.bool), s), "best": _like(torch.from_numpy(best), s),
+           "conf_best": conf_best, "mag_best": _like(torch.from_numpy(mag_best), s), "state_best": state_best}
+    if exchange:
+        x = more[0]
+        mag_quench = (2 * x["plus_quench"].cpu().numpy().reshape(R, K) - n) / n
+        out.update({"mag_quench": _like(torch.from_numpy(mag_quench), s),
+                    "exchanges": _like(x["exchanges"].view(R, K), s), "passes": _like(x["passes"].view(R, K), s),
+                    "converged": _like(x["converged"].view(R, K).to(torch.bool), s)})
+    if keep_all:
+        out["conf"] = _like(rows(out_np, torch.int8).view(R, K, n), s)
+    return out
 
 
 def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all=False, kernel=None, validate=True):
@@ -524,60 +648,30 @@ def quench_restarts(graph, s, p, c, restarts=1, orders=None, seed=None, keep_all
     and, with ``keep_all``, ``conf`` int8 (R, K, n).  numpy in -> numpy out,
     tensor in -> tensors on the input's device.  The input is never written;
     starts without consensus come back unchanged in every restart."""
-    p, c, T = _steps(p, c)
-    if kernel:
-        raise ValueError(f"unknown kernel options {sorted(dict(kernel))}")
-    stack, n, R = _host_shapes(graph, s)
-    K = int(restarts)
-    orders = _check_orders(orders, seed, K, R, n)
-    if stack:
-        adj = graph.cpu().numpy() if isinstance(graph, torch.Tensor) else np.asarray(graph)
-        if not np.issubdtype(adj.dtype, np.integer):
-            raise ValueError("the (R, n, d) graph stack must be an integer array")
-        if adj.size and (adj.min() < 0 or adj.max() >= n):
-            raise ValueError("adjacency index out of range")
-        d = int(adj.shape[2])
-        adj_t = _device.to_device(adj.astype(np.int32, copy=False))
-        graphs = [Graph("ell", n, d=d, adj=adj_t[r]) for r in range(R)]
-        g = graphs[0]
-    else:
-        g = as_graph(graph)
-        graphs = [g]
-    if validate:
-        for gr in graphs:
-            _check_symmetric(gr)
-    caps = _caps(g, T)                      # ELL: a function of (n, d) alone, the same for every graph of a stack
-    lib = _lib.load()
-    lds = int(lib.mjx_quench_jobs_lds(n, T, caps))
-    if lds < 0:
-        raise ValueError(f"quench_restarts: a job of n = {n}, p + c - 1 = {T} (ball bound {list(caps)}) does not fit "
-                         "the workgroup's LDS; quench is the path for this shape")
-    t, vector = _spins_2d(s)
-    dev, st, Wn = t.device, _device.stream_handle(), (n + 63) // 64
-    s_np = torch.empty((R, Wn), dtype=torch.int64, device=dev)
-    code, step = _device.dtype_code(t), n * t.element_size()
-    for r in range(R):
-        _lib.call("mjx_pack_np", t.data_ptr() + r * step, code, n, s_np.data_ptr() + r * Wn * 8, st)
-    order_t = _device.to_device(orders)
-    out_np, flipped, plus, consensus = _run_jobs(g, adj_t if stack else None, R, K, p, c, caps, s_np, order_t)
-    sums = 2 * plus.cpu().numpy().reshape(R, K) - n
-    best = pick_best(sums)
-    # sum(s) / n as numpy divides two integers, as quench does
-    mag = sums / n
-    mag_best = mag[np.arange(R), best]
-    state_best = out_np.view(R, K, Wn)[torch.arange(R, device=dev), torch.from_numpy(best).to(dev)].contiguous()
+    return _quench_jobs("quench_restarts", graph, s, p, c, restarts, orders, seed, keep_all, kernel, validate)
 
-    def rows(bits, dtype):
-        conf = torch.empty((bits.shape[0], n), dtype=dtype, device=dev)
-        dc, row = _device.dtype_code(conf), n * conf.element_size()
-        for j in range(bits.shape[0]):
-            _lib.call("mjx_unpack_np", bits.data_ptr() + j * Wn * 8, n, conf.data_ptr() + j * row, dc, st)
-        return conf
 
-    conf_best = _conf_like(rows(state_best, t.dtype), s, vector)
-    out = {"mag": _like(torch.from_numpy(mag), s), "flipped": _like(flipped.view(R, K), s),
-           "consensus": _like(consensus.to(torch.bool), s), "best": _like(torch.from_numpy(best), s),
-           "conf_best": conf_best, "mag_best": _like(torch.from_numpy(mag_best), s), "state_best": state_best}
-    if keep_all:
-        out["conf"] = _like(rows(out_np, torch.int8).view(R, K, n), s)
-    return out
+def quench_exchange(graph, s, p, c, restarts=1, orders=None, seed=None, max_passes=8, keep_all=False, kernel=None,
+                    validate=True):
+    """``quench_restarts`` with the (1, 2) exchange descent behind every job's
+    pass: the move that leaves a single-flip local minimum downwards.
+
+    After its quench pass a job walks its order again, up to ``max_passes``
+    times: every -1 node j in turn becomes +1 (consensus is kept), the +1
+    nodes are tried for removal in the job's order, and the add stays when two
+    or more of them dropped (a net loss of at least one +1 spin); otherwise
+    the state is as it was.  The passes end with the first one that commits
+    nothing.  The result is again a single-flip local minimum, never heavier
+    than the pass's, and equal, bit for bit, to the walk that tries every +1
+    node (include/mjx.h has the definition, DESIGN.md why the kernel may try
+    only the nodes near the add).
+
+    Inputs, orders / ``seed`` rule, graph forms and refusals as
+    ``quench_restarts``; p + c - 1 <= 3 and ``max_passes`` >= 1.  Returns
+    ``quench_restarts``'s dict (``mag``, ``flipped`` (of the quench pass),
+    ``best``, ``conf_best``, ... describe the results after the descent) plus,
+    all (R, K): ``mag_quench`` float64 (sum(s)/n after the quench pass alone),
+    ``exchanges`` int64 (adds that stayed), ``passes`` int64 (walked; 0 without
+    consensus) and ``converged`` bool (the last pass committed nothing)."""
+    return _quench_jobs("quench_exchange", graph, s, p, c, restarts, orders, seed, keep_all, kernel, validate,
+                        exchange=True, max_passes=max_passes)
