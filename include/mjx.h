@@ -1123,6 +1123,65 @@ int mjx_census_mask_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, i
 int mjx_census_minima(const uint64_t* mask, int64_t n, int T, int64_t block_lo, int64_t block_hi, int grid,
                       unsigned long long* minima, unsigned long long* heaviest_key, void* stream);
 
+/* ---- attractor census: where all 2^n starts of a small graph end up -------- */
+/*
+ * The census above looks at a fixed horizon and at one outcome; this one runs
+ * every start configuration to its attractor.  Graph, rule, configuration
+ * index x, weight k = popcount(x) and 64-config blocks as for mjx_census_*.
+ *   Trajectory: s(0) = x, s(t+1) = onestep(s(t)).
+ *   p = min{t >= 0 : s(t+2) = s(t)}, c = 1 if s(p+1) = s(p), else 2 -- the
+ *     definitions of mjx_attractor_record, exactly.
+ *   Class of x:  0 plus   c = 1 and s(p) is all +1
+ *                1 minus  c = 1 and s(p) is all -1
+ *                2 fixed  c = 1, neither of the above
+ *                3 cycle  c = 2
+ *     A configuration with p > t_max is unsettled and belongs to no class.
+ *   hist[class][p][k], (4, t_max+1, n+1): the number of x of weight k in that
+ *     class with transient exactly p.  unsettled[k], (n+1).  Per weight they
+ *     add up to C(n, k).  The cumulative sum of hist[0] over p <= t is
+ *     counts[t] of the census, for every horizon t <= t_max.
+ *   keys[0], lightest_plus: the smallest (k, x) over class plus, any p, as
+ *     k << 48 | x under an atomic min (the caller starts it at all ones; all +1
+ *     is in the class, so a full enumeration always finds one).
+ *   keys[1], longest: the largest (p, x) over the settled configurations, as
+ *     p << 48 | x under an atomic max (the caller starts it at 0, which is the
+ *     key of all -1: a fixed point, p = 0, x = 0; a range without a settled
+ *     configuration leaves the word alone).
+ *   Neither key depends on the launch geometry or the split of the range.
+ *
+ * The frame of the census kernel: a lane owns one block at a time, level 0 is
+ * generated, the adjacency sits in LDS as bytes, the workgroup is one wave.
+ * Two LDS level buffers: sweep t reads s(t-1) from one and writes s(t) over
+ * s(t-2) in the other, comparing with both before the store.  A wave sweeps
+ * until each of its 64 x 64 configurations has settled, at most t_max + 2
+ * times.  The workgroup's counts are 32-bit LDS cells flushed with 64-bit
+ * global atomics at the end; a launch covers at most 2^25 blocks (2^31
+ * configurations), so no cell can wrap.  mjx_attractor_census_lds(n, t_max) =
+ *   1024 n + 16 (t_max + 1)(n + 1) + 8 ceil((n + 1) / 2) + 16 + 8 n
+ *   + 8 ceil((n + 1) / 4) + 8 ceil(47 n / 8)
+ * bytes: 52,176 at n = 32, t_max = 32; -1 for n outside 1..48, t_max outside
+ * 0..1024, or more than 65,536 bytes (no dynamic-LDS opt-in).
+ *
+ * hist, unsettled: device, ADDED to (64-bit atomics); keys: device [2] as
+ * above; so [0, B) may be split over launches into the same buffers.  flag: as
+ * for mjx_census_* (bit 1 = an adjacency entry outside 0..n-1, bit 2 = a bad
+ * CSR row); the kernel then stops in bounds and writes nothing else.  stats:
+ * NULL, or device [2] ADDED to: the 64-block rows the waves ran and the sweeps
+ * they made (sweeps / rows = the mean number of sweeps of a wave).  grid: 0 =
+ * the library's choice, > 0 forces the number of workgroups.
+ * MJX_ERANGE: n > 48, t_max > 1024, d > 47, block_hi - block_lo > 2^25.
+ * MJX_EINVAL: n < 1, t_max < 0, an LDS demand past 65,536 bytes, a block range
+ * outside 0 <= block_lo <= block_hi <= B, grid < 0, a NULL pointer (stats
+ * excepted).  No allocation, no host synchronisation.
+ */
+int64_t mjx_attractor_census_lds(int64_t n, int t_max);
+int mjx_attractor_census_ell(const int32_t* adj, int64_t n, int d, int t_max, int64_t block_lo, int64_t block_hi,
+                             int grid, unsigned long long* hist, unsigned long long* unsettled,
+                             unsigned long long* keys, int32_t* flag, unsigned long long* stats, void* stream);
+int mjx_attractor_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int t_max, int64_t block_lo,
+                             int64_t block_hi, int grid, unsigned long long* hist, unsigned long long* unsettled,
+                             unsigned long long* keys, int32_t* flag, unsigned long long* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

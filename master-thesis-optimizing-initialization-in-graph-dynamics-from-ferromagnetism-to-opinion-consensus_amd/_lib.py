@@ -168,6 +168,9 @@ SIGNATURES = {
     "mjx_census_mask_ell": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_mask_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_minima": [c_vp, c_i64, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
+    "mjx_attractor_census_lds": [c_i64, c_int],
+    "mjx_attractor_census_ell": [c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_attractor_census_csr": [c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "mjx_last_hip_error": ctypes.c_char_p,
              "mjx_sa_lightcone_lds": c_i64, "mjx_sa_lds_bytes": c_i64, "mjx_sa_lds_plan": c_i64, "mjx_bdcm_lds_bytes": c_i64, "mjx_bdcm_scratch_bytes": c_i64,
@@ -177,7 +180,7 @@ _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "
              "mjx_quench_lds": c_i64, "mjx_flip_gain_scratch_bytes": c_i64, "mjx_quench_scratch_bytes": c_i64,
              "mjx_quench_regions_scratch_bytes": c_i64, "mjx_quench_jobs_lds": c_i64,
              "mjx_quench_exchange_jobs_lds": c_i64,
-             "mjx_census_lds": c_i64}
+             "mjx_census_lds": c_i64, "mjx_attractor_census_lds": c_i64}
 
 MJX_OK, MJX_EINVAL, MJX_EHIP, MJX_ERANGE = 0, 1, 2, 3      # status codes (include/mjx.h)
 MJX_I8, MJX_I32, MJX_I64 = 1, 4, 8

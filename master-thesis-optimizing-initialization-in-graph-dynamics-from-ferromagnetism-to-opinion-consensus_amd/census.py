@@ -19,9 +19,16 @@ blocks over launches of at most ``chunk_blocks`` each.
 ``census_minima`` keeps the membership bit of every x and counts, from that
 bitmap, the minimal elements of every level: the local minima of the quenches.
 
+``attractor_census`` runs every x to its attractor instead of a fixed horizon:
+how many starts of each weight end all +1, all -1, in another fixed point or in
+a 2-cycle, and after how many steps -- the exact counterpart of
+``consensus_curve``.
+
 Not covered: several devices (the block range makes it a host loop), n > 48,
 symmetry reduction.  There is no CPU fallback.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -33,8 +40,14 @@ from .quench import _steps
 N_MAX = 48
 DEG_MAX = 47
 # blocks of 64 configurations per launch: 2^26 configurations, a fraction of a millisecond of
-# kernel at n = 32, so no single launch holds a shared device for long (census)
+# kernel at n = 32 (about 2 ms for the attractor census, which sweeps until every configuration has
+# settled), so no single launch holds a shared device for long (census)
 CHUNK_BLOCKS = 1 << 20
+# attractor_census: the classes in the order of hist's first axis, the kernel's limits (include/mjx.h)
+CLASSES = ("plus", "minus", "fixed", "cycle")
+T_MAX_CAP = 1024
+LDS_MAX = 64 * 1024
+LAUNCH_BLOCKS_MAX = 1 << 25            # 32-bit LDS cells: a launch counts at most 2^31 configurations
 
 
 def _kernel_options(kernel):
@@ -107,10 +120,10 @@ def _run(g, p, c, block_lo, block_hi, chunk, grid, mask=None):
     return counts, keys
 
 
-def _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=False):
-    """The host refusals of ``census`` -> (graph, p, c, n, blocks, chunk, grid); ``mask``: the refusal of a
-    large 2^n names the bytes of the bitmap."""
-    p, c, T = _steps(p, c)
+def _checked_enumeration(graph, max_configs, chunk_blocks, kernel, bitmap_levels=0, fits=None):
+    """The host refusals every enumeration shares -> (graph, n, blocks, chunk, grid); ``bitmap_levels``:
+    the refusal of a large 2^n names the bytes of a bitmap of that many levels; ``fits(n)``: the caller's
+    own refusal of a shape, made before the graph goes to the device."""
     grid = _kernel_options(kernel)
     n = _host_n(graph)
     if n < 1:
@@ -120,14 +133,24 @@ def _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=False):
     configs = 1 << n
     if configs > int(max_configs):
         raise ValueError(f"census: 2^{n} = {configs} configurations exceed max_configs = {int(max_configs)}"
-                         + (f"; the bitmap of the {T + 1} levels would take (T+1) * 2^n / 8 = "
-                            f"{(T + 1) * max(configs, 64) // 8} bytes" if mask else ""))
+                         + (f"; the bitmap of the {bitmap_levels} levels would take (T+1) * 2^n / 8 = "
+                            f"{bitmap_levels * max(configs, 64) // 8} bytes" if bitmap_levels else ""))
     blocks = 1 << max(n - 6, 0)
     chunk = CHUNK_BLOCKS if chunk_blocks is None else int(chunk_blocks)
     if chunk < 1:
         raise ValueError("chunk_blocks must be >= 1")
+    if fits is not None:
+        fits(n)
     _check_rows(_host_rows(graph), n)
-    return as_graph(graph), p, c, n, blocks, chunk, grid
+    return as_graph(graph), n, blocks, chunk, grid
+
+
+def _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=False):
+    """The host refusals of ``census`` -> (graph, p, c, n, blocks, chunk, grid); ``mask``: the refusal of a
+    large 2^n names the bytes of the bitmap."""
+    p, c, T = _steps(p, c)
+    g, n, blocks, chunk, grid = _checked_enumeration(graph, max_configs, chunk_blocks, kernel, (T + 1) if mask else 0)
+    return g, p, c, n, blocks, chunk, grid
 
 
 def _spins(key, n):
@@ -218,3 +241,87 @@ def census_minima(graph, p, c, *, max_configs=2 ** 34, chunk_blocks=None, kernel
     if return_mask:
         res["mask"] = mask
     return res
+
+
+def attractor_census_lds(n, t_max):
+    """LDS bytes of a workgroup of the attractor census (mjx_attractor_census_lds without its ceiling): two
+    levels, hist[4][t_max+1][n+1] and unsettled[n+1] as 32-bit cells, two keys, level-0 patterns, row offsets,
+    neighbour bytes."""
+    return (1024 * n + 16 * (t_max + 1) * (n + 1) + 8 * (-(-(n + 1) // 2)) + 16 + 8 * n + 8 * (-(-(n + 1) // 4))
+            + 8 * (-(-(DEG_MAX * n) // 8)))
+
+
+def _run_attractor(g, t_max, block_lo, block_hi, chunk, grid, stats=False):
+    """Blocks [block_lo, block_hi) in launches of at most ``chunk`` blocks -> (hist int64 (4, t_max+1, n+1),
+    unsettled int64 (n+1,), keys int64 (2,): lightest plus and longest as signed words, stats int64 (2,) or
+    None: rows of 64 blocks and sweeps), device tensors."""
+    n = g.n
+    dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
+    hist = torch.zeros((4, t_max + 1, n + 1), dtype=torch.int64, device=dev)
+    uns = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+    keys = torch.tensor([-1, 0], dtype=torch.int64, device=dev)             # all ones; 0
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    st8 = torch.zeros(2, dtype=torch.int64, device=dev) if stats else None
+    if g.kind == "ell":
+        name, ga = "mjx_attractor_census_ell", (_device.ptr(g.adj) if g.d else None, n, g.d)
+    else:
+        name, ga = "mjx_attractor_census_csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n)
+    st = _device.stream_handle()
+    out = (_device.ptr(hist), _device.ptr(uns), _device.ptr(keys), _device.ptr(flag),
+           _device.ptr(st8) if stats else None)
+    chunk = min(chunk, LAUNCH_BLOCKS_MAX)
+    for lo in range(block_lo, block_hi, chunk):
+        _lib.call(name, *ga, t_max, lo, min(block_hi, lo + chunk), grid, *out, st)
+    if int(flag.item()):
+        raise _lib.MjxError("attractor_census: an adjacency entry lies outside 0..n-1 or a row is longer than 47")
+    return hist, uns, keys, st8
+
+
+def attractor_census(graph, t_max=32, *, max_configs=2 ** 36, chunk_blocks=None, kernel=None):
+    """Run all 2^n start configurations of ``graph`` to their attractors and
+    count them by class, transient and weight.
+
+    With s(0) = x, s(t+1) = onestep(s(t)), p = min{t : s(t+2) = s(t)} and c = 1
+    if s(p+1) = s(p) else 2 (``attractor``'s definitions), x is ``plus`` (c = 1,
+    s(p) all +1), ``minus`` (c = 1, all -1), ``fixed`` (c = 1, neither) or
+    ``cycle`` (c = 2); p > ``t_max`` is unsettled and in no class.
+
+    graph, ``max_configs``, ``chunk_blocks`` (at most 2^25 take effect) and
+    ``kernel`` as for ``census``; 0 <= t_max <= 1024, and the workgroup's LDS,
+    1024 n + 16 (t_max+1)(n+1) + ..., must fit 64 KiB (n = 32 or 40 at
+    t_max = 32 do, n = 48 up to t_max = 16).
+
+    Returns a dict: ``hist`` int64 (4, t_max+1, n+1) [class, p, k], ``unsettled``
+    int64 (n+1,), ``configs`` = 2^n, ``classes`` = ("plus", "minus", "fixed",
+    "cycle"), ``reach_plus`` int64 (t_max+1, n+1) = cumsum of hist[0] over p
+    (``census``'s ``counts`` for every horizon), ``p_plus`` float64 (n+1,) =
+    sum_p hist[0, p, k] / C(n, k), the exact consensus curve, ``min_plus_ever``
+    (the smallest weight that ever reaches all +1), ``m_min_ever`` =
+    (2 min_plus_ever - n) / n, ``witness_plus`` int8 (n,) of +-1: the plus
+    configuration with the smallest (weight, x), ``p_longest`` and
+    ``witness_longest`` int8 (n,): the settled configuration with the largest
+    (p, x), and ``mean_sweeps``: the sweeps a wave made on average."""
+    t_max = int(t_max)
+    if t_max < 0 or t_max > T_MAX_CAP:
+        raise ValueError(f"attractor_census: t_max = {t_max}; need 0 <= t_max <= {T_MAX_CAP}")
+
+    def fits(n):
+        lds = attractor_census_lds(n, t_max)
+        if lds > LDS_MAX:
+            raise ValueError(f"attractor_census: n = {n}, t_max = {t_max} need {lds} bytes of LDS per workgroup, "
+                             f"more than {LDS_MAX}: lower t_max")
+
+    g, n, blocks, chunk, grid = _checked_enumeration(graph, max_configs, chunk_blocks, kernel, fits=fits)
+    hist, uns, keys, st8 = _run_attractor(g, t_max, 0, blocks, chunk, grid, stats=True)
+    key = keys.cpu().numpy().view(np.uint64)
+    if key[0] == np.uint64(0xFFFFFFFFFFFFFFFF):                             # all +1 is a fixed point, p = 0
+        raise _lib.MjxError("attractor_census: no configuration reached all +1")
+    h = hist.cpu().numpy()
+    rows, sweeps = (int(v) for v in st8.cpu().numpy())
+    binom = np.array([math.comb(n, k) for k in range(n + 1)], dtype=np.float64)
+    min_plus = int(key[0] >> np.uint64(48))
+    return {"hist": h, "unsettled": uns.cpu().numpy(), "configs": 1 << n, "classes": CLASSES,
+            "reach_plus": np.cumsum(h[0], axis=0), "p_plus": h[0].sum(axis=0) / binom,
+            "min_plus_ever": min_plus, "m_min_ever": (2 * min_plus - n) / n, "witness_plus": _spins(key[:1], n)[0],
+            "p_longest": int(key[1] >> np.uint64(48)), "witness_longest": _spins(key[1:], n)[0],
+            "mean_sweeps": sweeps / rows}

@@ -1,4 +1,4 @@
-"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm|attractor|quench|census`` run the reference's three
+"""Script-shaped fronts: ``python -m mjx sa|sa-er|hpr|bdcm|attractor|quench|census|attractor-census`` run the reference's three
 experiments with its module constants as flags -- same names, same defaults --
 and write its np.savez keys.
 
@@ -40,6 +40,12 @@ and write its np.savez keys.
         configs, edges.  ``--minima`` adds the census of the minimal consensus
         sets, the local minima of the quenches (census.census_minima): minima,
         minima_total, max_plus, m_max, witness_max, mean_plus
+  attractor-census  no reference script: the attractor census
+        (census.attractor_census) of one such graph, every one of the 2^n
+        starts run until s(t+2) = s(t) (at most t_max + 2 steps); output
+        "attractor_census_{graph}.npz": hist, unsettled, configs, classes,
+        reach_plus, p_plus, min_plus_ever, m_min_ever, witness_plus, p_longest,
+        witness_longest, mean_sweeps, edges
 
 Added beside the reference's constants: ``--seed`` (the reference seeds
 nothing), ``--graph-seed``, ``--replicas`` (N_stat / n_rep / num_rep by
@@ -220,6 +226,16 @@ def build_parser():
     ce.add_argument("--minima", action="store_true",
                     help="also count the minimal consensus sets of every level, the local minima of the quenches")
     ce.add_argument("--out", default=None, help="output .npz (default: census_{graph}.npz)")
+    ac = sub.add_parser("attractor-census", help="run all 2^n starts of a small graph to their attractors and count "
+                                                 "them by class, transient and weight (no reference script)")
+    ac.add_argument("--graph", choices=("rrg", "er"), default="rrg")
+    ac.add_argument("--n", type=int, default=24, help="nodes (at most 48; 2^n configurations are run)")
+    ac.add_argument("--d", type=int, default=3, help="degree (rrg)")
+    ac.add_argument("--deg", type=float, default=2.0, help="mean degree (er; prob = deg/(n-1))")
+    ac.add_argument("--graph-seed", type=int, default=0, help="seed of the graph")
+    ac.add_argument("--t-max", type=int, default=32, help="a transient p > t_max is counted as unsettled")
+    ac.add_argument("--max-configs", type=int, default=None, help="refuse a larger 2^n (default 2^36)")
+    ac.add_argument("--out", default=None, help="output .npz (default: attractor_census_{graph}.npz)")
     return ap
 
 
@@ -422,10 +438,9 @@ def run_quench(a):
     return res
 
 
-def run_census(a):
-    from .census import census, census_minima
+def _small_graph(a):
+    """The graph of the census subcommands -> (graph, its edges u < v as int64 (m, 2))."""
     from .graph import Graph, erdos_renyi, random_regular_graph
-    t0 = time.time()
     if a.graph == "rrg":
         adj = random_regular_graph(a.d, a.n, seed=a.graph_seed)
         g = adj
@@ -436,10 +451,17 @@ def run_census(a):
         g = Graph.csr(rp, col)
         u = np.repeat(np.arange(a.n), np.diff(rp))
         v = np.asarray(col)
+    keep = u < v
+    return g, np.stack([u[keep], v[keep]], axis=1).astype(np.int64)
+
+
+def run_census(a):
+    from .census import census, census_minima
+    t0 = time.time()
+    g, edges = _small_graph(a)
     limit = {} if a.max_configs is None else {"max_configs": a.max_configs}
     res = (census_minima if a.minima else census)(g, a.p, a.c, **limit)
-    keep = u < v
-    res["edges"] = np.stack([u[keep], v[keep]], axis=1).astype(np.int64)
+    res["edges"] = edges
     out = a.out or f"census_{a.graph}.npz"
     np.savez(out, **res)
     print(f"census: {a.graph} n={a.n}, 2^{a.n} configurations, p={a.p} c={a.c}: min_plus "
@@ -452,10 +474,27 @@ def run_census(a):
     return res
 
 
+def run_attractor_census(a):
+    from .census import attractor_census
+    t0 = time.time()
+    g, edges = _small_graph(a)
+    limit = {} if a.max_configs is None else {"max_configs": a.max_configs}
+    res = attractor_census(g, a.t_max, **limit)
+    res["edges"] = edges
+    out = a.out or f"attractor_census_{a.graph}.npz"
+    np.savez(out, **res)
+    print(f"attractor-census: {a.graph} n={a.n}, 2^{a.n} configurations, t_max={a.t_max}: "
+          f"{dict(zip(res['classes'], res['hist'].sum(axis=(1, 2)).tolist()))}, unsettled "
+          f"{int(res['unsettled'].sum())}, min_plus_ever {res['min_plus_ever']} (m_min {res['m_min_ever']:.4f}), "
+          f"longest transient {res['p_longest']}, {res['mean_sweeps']:.2f} sweeps a wave, "
+          f"{time.time() - t0:.1f} s -> {out}", flush=True)
+    return res
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
     return {"sa": run_sa, "sa-er": run_sa_er, "hpr": run_hpr, "bdcm": run_bdcm, "attractor": run_attractor,
-            "quench": run_quench, "census": run_census}[a.cmd](a)
+            "quench": run_quench, "census": run_census, "attractor-census": run_attractor_census}[a.cmd](a)
 
 
 if __name__ == "__main__":

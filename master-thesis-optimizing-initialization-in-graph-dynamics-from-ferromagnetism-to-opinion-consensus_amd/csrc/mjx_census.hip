@@ -363,9 +363,234 @@ static int census_run(Adj A, int64_t n, int p, int c, int64_t block_lo, int64_t 
     return MJX_OK;
 }
 
+// ---- attractor census (definitions in include/mjx.h) ----------------------------------------------
+// k_census's frame -- a lane per block, level 0 generated, the adjacency as bytes in LDS, one wave per
+// workgroup, wave-uniform control flow -- run to the attractor instead of a fixed horizon.  Two level
+// buffers: sweep t reads s(t-1) from buf[(t-1) & 1] and writes s(t) over s(t-2) in buf[t & 1], and before
+// the store ORs new ^ s(t-2) into chg2 and new ^ s(t-1) into chg1 and keeps the AND and the OR of the new
+// words.  Sweep 1 is cn_sweep<true> (from the generated level 0), sweep 2 compares against the generated
+// level 0, from sweep 3 on everything is in place.  A bit of the lane's word `unsettled` leaves after
+// the first sweep t >= 2 whose chg2 bit is 0: p = t - 2, and chg1 / AND / OR of that sweep name the class.
+constexpr int ACN_MAXT = 1024;                // t_max at most; the LDS ceiling is reached sooner for n >= 4
+constexpr int64_t ACN_MAXBLOCKS = (int64_t)1 << 25;    // blocks per launch: the LDS cells are 32 bits wide
+
+// bytes of the parts of a workgroup's LDS, in this order
+struct AcLds {
+    size_t state, hist, uns, keys, pat, off, nbr;
+    __host__ __device__ size_t total() const { return state + hist + uns + keys + pat + off + nbr; }
+};
+
+__host__ __device__ inline AcLds ac_lds(int64_t n, int64_t t_max) {
+    const CnLds C = cn_lds(n);
+    AcLds L;
+    L.state = C.state;                                               // two levels [node][lane]
+    L.hist = (size_t)4 * (t_max + 1) * (n + 1) * sizeof(uint32_t);   // [class][p][k], a multiple of 8
+    L.uns = ((size_t)(n + 1) * sizeof(uint32_t) + 7) / 8 * 8;        // unsettled[k]
+    L.keys = 2 * sizeof(u64);                                        // lightest plus, longest
+    L.pat = C.pat;
+    L.off = C.off;
+    L.nbr = C.nbr;
+    return L;
+}
+
+struct AcTrack {
+    u64 chg1, chg2, all, any;    // OR of new ^ s(t-1), OR of new ^ s(t-2), AND and OR of the new words
+};
+
+// One tracked sweep: level t (>= 2) of the lane's block from level t-1 in `src`, written over level t-2
+// in `dst`.  SECOND (t = 2): level t-2 is level 0, generated from b and the pattern table `pat` as in
+// cn_sweep<true>; else it is the word the store replaces.  Wave-uniform control flow.
+template <bool SECOND>
+__device__ __forceinline__ AcTrack ac_sweep(int n, int fixed, const uint16_t* __restrict__ off,
+                                            const uint8_t* __restrict__ nbr, const u64* __restrict__ pat,
+                                            const u64* src, u64* dst, u64 b, int lane) {
+    AcTrack k = {0, 0, ~0ull, 0};
+    auto word = [&](int u) -> u64 { return src[u * 64 + lane]; };
+    auto put = [&](int v, u64 nw, u64 own) {
+        const u64 old = SECOND ? (pat[v] | (0 - ((b >> ((v + 58) & 63)) & 1))) : dst[v * 64 + lane];
+        k.chg2 |= nw ^ old;
+        k.chg1 |= nw ^ own;
+        k.all &= nw;
+        k.any |= nw;
+        dst[v * 64 + lane] = nw;
+    };
+    if (fixed == 3) {
+#pragma unroll 8
+        for (int v = 0; v < n; ++v) {
+            const uint8_t* row = nbr + 3 * v;
+            const u64 x[3] = {word(row[0]), word(row[1]), word(row[2])};
+            put(v, majority_fixed<3>(x, 0), word(v));
+        }
+    } else if (fixed == 4) {
+#pragma unroll 8
+        for (int v = 0; v < n; ++v) {
+            const uint8_t* row = nbr + 4 * v;
+            const u64 x[4] = {word(row[0]), word(row[1]), word(row[2]), word(row[3])};
+            const u64 own = word(v);
+            put(v, majority_fixed<4>(x, own), own);
+        }
+    } else {
+        for (int v = 0; v < n; ++v) {
+            const int e0 = off[v], e1 = off[v + 1];
+            BitCounter<6> bc;                                        // degree <= 47; degree 0 keeps the word
+            bc.reset();
+            for (int e = e0; e < e1; ++e) bc.add(word(nbr[e]));
+            const u64 own = word(v);
+            put(v, bc.majority(e1 - e0, own), own);
+        }
+    }
+    return k;
+}
+
+// the configurations m of the lane's block into row[k], k = kb + the weight of the low six bits
+__device__ __forceinline__ void ac_count(uint32_t* row, u64 m, int kb) {
+    if (__ballot(m != 0) == 0) return;
+#pragma unroll
+    for (int w = 0; w <= 6; ++w) {
+        const u64 x = m & cn_weight(w);
+        if (x) atomicAdd(&row[kb + w], (uint32_t)__popcll(x));
+    }
+}
+
+template <class Adj>
+__global__ void __launch_bounds__(64) k_attractor_census(Adj A, int n, int t_max, u64 block_lo, u64 block_hi,
+                                                         u64* __restrict__ hist_out, u64* __restrict__ uns_out,
+                                                         u64* __restrict__ keys, int32_t* __restrict__ flag,
+                                                         u64* __restrict__ stats) {
+    extern __shared__ __align__(8) unsigned char ac_smem[];
+    const AcLds L = ac_lds(n, t_max);
+    u64* buf = (u64*)ac_smem;
+    uint32_t* hist = (uint32_t*)(ac_smem + L.state);
+    uint32_t* uns = (uint32_t*)(ac_smem + L.state + L.hist);
+    u64* best = (u64*)(ac_smem + L.state + L.hist + L.uns);          // [0] smallest plus key, [1] largest (p, x) key
+    u64* pat = (u64*)(ac_smem + L.state + L.hist + L.uns + L.keys);
+    uint16_t* off = (uint16_t*)(ac_smem + L.state + L.hist + L.uns + L.keys + L.pat);
+    uint8_t* nbr = ac_smem + L.state + L.hist + L.uns + L.keys + L.pat + L.off;
+    const int lane = threadIdx.x;
+    const int row = n + 1, plane = (t_max + 1) * row, cells = 4 * plane;
+
+    const int bad = A.load(n, off, nbr);
+    if (bad) {                                                       // wave-uniform
+        if (lane == 0) atomicOr(flag, bad);
+        return;
+    }
+    for (int i = lane; i < cells; i += 64) hist[i] = 0;
+    if (lane < row) uns[lane] = 0;
+    if (lane == 0) best[0] = ~0ull, best[1] = 0;
+    if (lane < n) pat[lane] = cn_pattern(lane);
+    __syncthreads();
+
+    const int fixed = A.fixed();
+    const u64 valid = n < 6 ? ((1ull << (1 << n)) - 1) : ~0ull;      // n < 6: 2^n configurations in block 0
+    const u64 stride = (u64)gridDim.x * 64;
+    u64 rows = 0, sweeps = 0;                                        // wave-uniform: for stats
+    for (u64 first = block_lo + (u64)blockIdx.x * 64; first < block_hi; first += stride) {
+        const u64 b = first + lane;
+        const int kb = __popcll(b);                                  // weight of the nodes >= 6
+        u64 unsettled = b < block_hi ? valid : 0;
+        cn_sweep<true>(n, fixed, off, nbr, pat, buf + (size_t)n * 64, b, lane);    // s(1)
+        int t = 1;
+#pragma unroll 1
+        while (t < t_max + 2 && __ballot(unsettled != 0)) {
+            ++t;
+            u64* dst = buf + (size_t)(t & 1) * n * 64;
+            const u64* src = buf + (size_t)((t - 1) & 1) * n * 64;
+            const AcTrack k = (t == 2) ? ac_sweep<true>(n, fixed, off, nbr, pat, src, dst, b, lane)
+                                       : ac_sweep<false>(n, fixed, off, nbr, pat, src, dst, b, lane);
+            const u64 newly = unsettled & ~k.chg2;                   // s(t) = s(t-2) for the first time: p = t - 2
+            unsettled &= k.chg2;
+            if (__ballot(newly != 0) == 0) continue;
+            uint32_t* at = hist + (t - 2) * row;
+            const u64 plus = newly & k.all, minus = newly & ~k.any, cycle = newly & k.chg1;
+            ac_count(at + plane, minus, kb);
+            ac_count(at + 2 * plane, newly & ~(plus | minus | cycle), kb);
+            ac_count(at + 3 * plane, cycle, kb);
+            if (__ballot(plus != 0)) {
+                u64 key = ~0ull;                                     // of the first weight that has a configuration
+#pragma unroll
+                for (int w = 6; w >= 0; --w) {
+                    const u64 x = plus & cn_weight(w);
+                    if (x) {
+                        atomicAdd(&at[kb + w], (uint32_t)__popcll(x));
+                        key = ((u64)(kb + w) << 48) | (b * 64 + (u64)__builtin_ctzll(x));
+                    }
+                }
+                key = cn_min64(key);
+                if (lane == 0) atomicMin(&best[0], key);
+            }
+            const u64 far = cn_max64(newly ? ((u64)(t - 2) << 48) | (b * 64 + (u64)(63 - __builtin_clzll(newly))) : 0);
+            if (lane == 0) atomicMax(&best[1], far);
+        }
+        ac_count(uns, unsettled, kb);                                // p > t_max
+        ++rows;
+        sweeps += (u64)t;
+    }
+    __syncthreads();
+    for (int i = lane; i < cells; i += 64)
+        if (hist[i]) atomicAdd(&hist_out[i], (u64)hist[i]);
+    if (lane < row && uns[lane]) atomicAdd(&uns_out[lane], (u64)uns[lane]);
+    if (lane == 0) {
+        if (best[0] != ~0ull) atomicMin(&keys[0], best[0]);
+        if (best[1]) atomicMax(&keys[1], best[1]);
+        if (stats) {
+            atomicAdd(&stats[0], rows);
+            atomicAdd(&stats[1], sweeps);
+        }
+    }
+}
+
+template <class Adj>
+static int attractor_census_run(Adj A, int64_t n, int t_max, int64_t block_lo, int64_t block_hi, int grid,
+                                unsigned long long* hist, unsigned long long* unsettled, unsigned long long* keys,
+                                int32_t* flag, unsigned long long* stats, void* stream) {
+    if (t_max < 0 || n < 1 || !hist || !unsettled || !keys || !flag || grid < 0) return MJX_EINVAL;
+    if (n > CN_MAXN || t_max > ACN_MAXT) return MJX_ERANGE;
+    const size_t lds = ac_lds(n, t_max).total();
+    if (lds > kCnLdsMax) return MJX_EINVAL;
+    const int64_t B = (int64_t)1 << (n > 6 ? n - 6 : 0);
+    if (block_lo < 0 || block_lo > block_hi || block_hi > B) return MJX_EINVAL;
+    // a workgroup's 32-bit LDS cell counts at most the 64 * 2^25 = 2^31 configurations of the launch
+    if (block_hi - block_lo > ACN_MAXBLOCKS) return MJX_ERANGE;
+    if (block_lo == block_hi) return MJX_OK;
+    int g = grid;                                                    // as census_run
+    if (!g) {
+        const int64_t per = std::min<int64_t>(32, (int64_t)(kCnLdsPerCu / lds));
+        g = (int)std::max<int64_t>(1, std::min<int64_t>((block_hi - block_lo + 63) / 64, device_cus() * per));
+    }
+    k_attractor_census<Adj><<<(unsigned)g, 64, lds, as_stream(stream)>>>(
+        A, (int)n, t_max, (u64)block_lo, (u64)block_hi, hist, unsettled, keys, flag, stats);
+    MJX_LAUNCH_CHECK("k_attractor_census");
+    return MJX_OK;
+}
+
 }  // namespace mjx
 
 using namespace mjx;
+
+extern "C" int64_t mjx_attractor_census_lds(int64_t n, int t_max) {
+    if (n < 1 || n > CN_MAXN || t_max < 0 || t_max > ACN_MAXT) return -1;
+    const size_t b = ac_lds(n, t_max).total();
+    return b > kCnLdsMax ? -1 : (int64_t)b;
+}
+
+extern "C" int mjx_attractor_census_ell(const int32_t* adj, int64_t n, int d, int t_max, int64_t block_lo,
+                                        int64_t block_hi, int grid, unsigned long long* hist,
+                                        unsigned long long* unsettled, unsigned long long* keys, int32_t* flag,
+                                        unsigned long long* stats, void* stream) {
+    if (d < 0 || (d > 0 && !adj)) return MJX_EINVAL;
+    if (d > CN_MAXDEG) return MJX_ERANGE;
+    return attractor_census_run(CnEll{adj, d}, n, t_max, block_lo, block_hi, grid, hist, unsettled, keys, flag, stats,
+                                stream);
+}
+
+extern "C" int mjx_attractor_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int t_max,
+                                        int64_t block_lo, int64_t block_hi, int grid, unsigned long long* hist,
+                                        unsigned long long* unsettled, unsigned long long* keys, int32_t* flag,
+                                        unsigned long long* stats, void* stream) {
+    if (!row_ptr) return MJX_EINVAL;                         // a graph without edges has no col array
+    return attractor_census_run(CnCsr{row_ptr, col}, n, t_max, block_lo, block_hi, grid, hist, unsettled, keys, flag,
+                                stats, stream);
+}
 
 extern "C" int64_t mjx_census_lds(int64_t n) {
     if (n < 1 || n > CN_MAXN) return -1;
