@@ -97,26 +97,29 @@ def _check_rows(rows, n):
                          "defined for undirected graphs")
 
 
+def _launch(stem, g, head, block_lo, block_hi, chunk, grid, out, tail, what):
+    """mjx_<stem>_{ell,csr}(graph, *head, lo, hi, grid, *out, flag, *tail, stream) on the blocks [block_lo,
+    block_hi) in launches of at most ``chunk`` blocks; raises when a kernel raised the flag.  ``out`` and
+    ``tail``: device tensors, or None."""
+    kind, ga = g.kernel_args()
+    flag = torch.zeros(1, dtype=torch.int32, device=g.device)
+    ptrs = [None if t is None else _device.ptr(t) for t in (*out, flag, *tail)]
+    st = _device.stream_handle()
+    for lo in range(block_lo, block_hi, chunk):
+        _lib.call(f"mjx_{stem}_{kind}", *ga, *head, lo, min(block_hi, lo + chunk), grid, *ptrs, st)
+    if int(flag.item()):
+        raise _lib.MjxError(f"{what}: an adjacency entry lies outside 0..n-1 or a row is longer than 47")
+
+
 def _run(g, p, c, block_lo, block_hi, chunk, grid, mask=None):
     """Blocks [block_lo, block_hi) in launches of at most ``chunk`` blocks -> (counts int64 (T+1, n+1), keys
     int64 (T+1,): the witness keys as signed words), device tensors.  ``mask``: a device int64 (T+1, B)
     tensor that receives the membership words of the blocks (the mask entry points)."""
     n, T = g.n, p + c - 1
-    dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
-    counts = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=dev)
-    keys = torch.full((T + 1,), -1, dtype=torch.int64, device=dev)           # all ones
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    kept = "" if mask is None else "mask_"
-    if g.kind == "ell":
-        name, ga = f"mjx_census_{kept}ell", (_device.ptr(g.adj) if g.d else None, n, g.d)
-    else:
-        name, ga = f"mjx_census_{kept}csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n)
-    st = _device.stream_handle()
-    out = (_device.ptr(counts), _device.ptr(keys), _device.ptr(flag)) + (() if mask is None else (_device.ptr(mask),))
-    for lo in range(block_lo, block_hi, chunk):
-        _lib.call(name, *ga, p, c, lo, min(block_hi, lo + chunk), grid, *out, st)
-    if int(flag.item()):
-        raise _lib.MjxError("census: an adjacency entry lies outside 0..n-1 or a row is longer than 47")
+    counts = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=g.device)
+    keys = torch.full((T + 1,), -1, dtype=torch.int64, device=g.device)      # all ones
+    _launch("census" if mask is None else "census_mask", g, (p, c), block_lo, block_hi, chunk, grid,
+            (counts, keys), () if mask is None else (mask,), "census")
     return counts, keys
 
 
@@ -217,8 +220,7 @@ def census_minima(graph, p, c, *, max_configs=2 ** 34, chunk_blocks=None, kernel
     also ``mask``, the device bitmap as int64 bit patterns (T+1, B),
     B = 2^max(n-6, 0): bit j of word b of level t is configuration 64 b + j."""
     g, p, c, n, blocks, chunk, grid = _checked(graph, p, c, max_configs, chunk_blocks, kernel, mask=True)
-    T = p + c - 1
-    dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
+    T, dev = p + c - 1, g.device
     mask = torch.empty((T + 1, blocks), dtype=torch.int64, device=dev)       # pass 1 writes every word
     counts, keys = _run(g, p, c, 0, blocks, chunk, grid, mask=mask)
     minima = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=dev)
@@ -255,25 +257,13 @@ def _run_attractor(g, t_max, block_lo, block_hi, chunk, grid, stats=False):
     """Blocks [block_lo, block_hi) in launches of at most ``chunk`` blocks -> (hist int64 (4, t_max+1, n+1),
     unsettled int64 (n+1,), keys int64 (2,): lightest plus and longest as signed words, stats int64 (2,) or
     None: rows of 64 blocks and sweeps), device tensors."""
-    n = g.n
-    dev = g.adj.device if g.kind == "ell" else g.row_ptr.device
+    n, dev = g.n, g.device
     hist = torch.zeros((4, t_max + 1, n + 1), dtype=torch.int64, device=dev)
     uns = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
     keys = torch.tensor([-1, 0], dtype=torch.int64, device=dev)             # all ones; 0
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
     st8 = torch.zeros(2, dtype=torch.int64, device=dev) if stats else None
-    if g.kind == "ell":
-        name, ga = "mjx_attractor_census_ell", (_device.ptr(g.adj) if g.d else None, n, g.d)
-    else:
-        name, ga = "mjx_attractor_census_csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, n)
-    st = _device.stream_handle()
-    out = (_device.ptr(hist), _device.ptr(uns), _device.ptr(keys), _device.ptr(flag),
-           _device.ptr(st8) if stats else None)
-    chunk = min(chunk, LAUNCH_BLOCKS_MAX)
-    for lo in range(block_lo, block_hi, chunk):
-        _lib.call(name, *ga, t_max, lo, min(block_hi, lo + chunk), grid, *out, st)
-    if int(flag.item()):
-        raise _lib.MjxError("attractor_census: an adjacency entry lies outside 0..n-1 or a row is longer than 47")
+    _launch("attractor_census", g, (t_max,), block_lo, block_hi, min(chunk, LAUNCH_BLOCKS_MAX), grid,
+            (hist, uns, keys), (st8,), "attractor_census")
     return hist, uns, keys, st8
 
 

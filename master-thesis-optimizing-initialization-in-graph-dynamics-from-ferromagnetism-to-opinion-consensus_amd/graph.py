@@ -360,3 +360,14 @@ class Graph:
     @property
     def nnz(self):
         return self.n * self.d if self.kind == "ell" else int(self.col.shape[0])
+
+    @property
+    def device(self):
+        return (self.adj if self.kind == "ell" else self.row_ptr).device
+
+    def kernel_args(self):
+        """(kind, the leading arguments of a ``mjx_*_<kind>`` entry point): ("ell", (adj, n, d)) or
+        ("csr", (row_ptr, col, n)); an array without entries (d = 0, nnz = 0) goes as None."""
+        if self.kind == "ell":
+            return "ell", (_device.ptr(self.adj) if self.d else None, self.n, self.d)
+        return "csr", (_device.ptr(self.row_ptr), _device.ptr(self.col) if self.nnz else None, self.n)

@@ -164,12 +164,6 @@ def _caps(g, T):
     return out
 
 
-def _graph_args(g):
-    if g.kind == "ell":
-        return "ell", (_device.ptr(g.adj) if g.d else None, g.n, g.d)
-    return "csr", (_device.ptr(g.row_ptr), _device.ptr(g.col) if g.nnz else None, g.n)
-
-
 def _scratch(nbytes, what, T, lds_entries, dev):
     if nbytes < 0 or _lib.load().mjx_quench_lds(T, lds_entries) < 0:
         raise ValueError(f"{what}: lds_entries = {lds_entries} does not fit the workgroup's LDS at p + c - 1 = {T}")
@@ -188,7 +182,7 @@ def _cone_call(entry, what, g, levels, R, p, c, T, caps, lds_entries, scratch_by
     dev = levels[0].device
     scratch = _scratch(scratch_bytes, what, T, lds_entries, dev)
     lv = (ctypes.c_void_p * (T + 1))(*[t.data_ptr() for t in levels])
-    kind, ga = _graph_args(g)
+    kind, ga = g.kernel_args()
 
     def call(*args):
         _lib.call(f"mjx_{entry}_{kind}_rp", *ga, R, p, c, lv, caps, lds_entries, _device.ptr(scratch),
