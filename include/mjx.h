@@ -1018,6 +1018,78 @@ int mjx_quench_exchange_jobs_csr(const int64_t* row_ptr, const int32_t* col, int
                                  int64_t* passes, uint8_t* converged, uint8_t* consensus, int32_t* flag,
                                  int64_t* stats, void* stream);
 
+/* ---- Metropolis add / drop inside the consensus set ------------------------ */
+/*
+ * Every pass above is a descent and stops at the first state its move set
+ * cannot leave.  This one walks INSIDE the consensus set at a finite
+ * temperature: Metropolis on the up-set {z : consensus(z)}, consensus(z) =
+ * "onestep^T(z) is all +1", T = p + c - 1, with energy = the weight (number of
+ * +1 spins) and inverse temperature beta_u in sweep u.  A drop that keeps
+ * consensus lowers the energy and is always taken, a drop that leaves the set
+ * is refused, an add (never leaves the set: the rule is monotone) is taken with
+ * probability e^{-beta_u}.  It is the chain of code/SA_RRG.py in the limit
+ * b -> infinity, started inside the set instead of stopping at its border.
+ *
+ * Per job (start r, restart k; jobs, orders, graphs, s_np, caps and the first
+ * outputs as mjx_quench_jobs_*), with a 64-bit seed, sweeps = U >= 0 and a
+ * device array thr of U uint32:
+ *
+ *   x = start
+ *   if not consensus(x): result = start; flipped = 0;
+ *                        plus_quench = plus_best = plus(start); best_sweep = 0;
+ *                        adds = drops = refused = 0; trace[u] = plus(start)
+ *   x = the quench pass over ord (flipped = its count); plus_quench = plus(x)
+ *   best = x; plus_best = plus_quench; best_sweep = 0
+ *   for u = 0 .. U-1:
+ *       for q = 0 .. n-1:
+ *           (w0, w1, _, _) = philox4x32_10(counter = (q, u, r, k),
+ *                                          key = (seed & 0xffffffff, seed >> 32))
+ *           i = (w0 * n) >> 32                        (64-bit product)
+ *           if x[i] = +1: if consensus(x - i): x = x - i, drops += 1
+ *                         else refused += 1
+ *           else:         if w1 < thr[u]:     x = x + i, adds += 1
+ *       trace[u] = plus(x)
+ *       if plus(x) < plus_best: best = x; plus_best = plus(x); best_sweep = u + 1
+ *   result = the quench pass over ord from best; plus = plus(result)
+ *
+ * thr[u] = min(floor(e^{-beta_u} * 2^32), 2^32 - 1), computed by the caller in
+ * float64: the device evaluates no exponential and the results are bit-exact.
+ * The counter holds (r, k), not the job index, so a job keeps its stream
+ * whatever R and K are.  The result is a consensus single-flip local minimum;
+ * plus <= plus_best <= plus_quench, so a job is never worse than the same job
+ * of mjx_quench_jobs_*; U = 0 gives exactly that call's output.  T = 0:
+ * consensus is "all +1", every proposal is refused.
+ *
+ * One wave runs a job; its LDS is the quench job's plus one bitmap, the
+ * snapshot `best`:
+ *   mjx_quench_anneal_jobs_lds(n, T, caps) =
+ *     mjx_quench_jobs_lds(n, T, caps) + 4 * 2 * ceil(n/64), rounded up to 16;
+ *   -1 as mjx_quench_jobs_lds, or past the same 64 KiB.
+ * T = 0..6 as mjx_quench_jobs_* (no ball of radius 2T is needed).
+ * Further outputs, device arrays: plus_quench, plus_best, best_sweep int64
+ * [R*K]; moves int64 [R*K][3] = adds, drops, refused; trace NULL or int32
+ * [R*K][U].  flag: bits 0 and 1 as mjx_quench_jobs_*, bit 2 = an accepted add
+ * did not commit (a bug, never an input error).  The results of a flagged job
+ * are void; its trace is written only up to the sweep before the one it
+ * stopped in, the rest is left as the caller passed it.
+ * MJX_EINVAL: as mjx_quench_jobs_*, sweeps < 0 or >= 2^31, thr NULL with
+ * sweeps > 0, a NULL output other than trace, a shape that does not fit.  No
+ * allocation, no host synchronisation.
+ */
+int64_t mjx_quench_anneal_jobs_lds(int64_t n, int T, const int64_t* caps);
+int mjx_quench_anneal_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t graph_stride, int64_t R, int64_t K, int p,
+                               int c, const int64_t* caps, int64_t sweeps, const uint32_t* thr, uint64_t seed,
+                               const uint64_t* s_np, const int32_t* order, int64_t order_stride_r, uint64_t* out_np,
+                               int64_t* flipped, int64_t* plus, int64_t* plus_quench, int64_t* plus_best,
+                               int64_t* best_sweep, int64_t* moves, int32_t* trace, uint8_t* consensus, int32_t* flag,
+                               void* stream);
+int mjx_quench_anneal_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int64_t K, int p,
+                               int c, const int64_t* caps, int64_t sweeps, const uint32_t* thr, uint64_t seed,
+                               const uint64_t* s_np, const int32_t* order, int64_t order_stride_r, uint64_t* out_np,
+                               int64_t* flipped, int64_t* plus, int64_t* plus_quench, int64_t* plus_best,
+                               int64_t* best_sweep, int64_t* moves, int32_t* trace, uint8_t* consensus, int32_t* flag,
+                               void* stream);
+
 /* ---- exact consensus census of a small graph ------------------------------- */
 /*
  * Ground truth by exhaustive enumeration: every start configuration of a graph

@@ -15,7 +15,7 @@ from .npz import (save_sa_npz, save_hpr_npz, save_bdcm_npz, sa_arrays, hpr_array
                   graphs_from_npz)
 from .dynamics import onestep_majority, s_endstate, m, pack, unpack, rollout, popcount, as_graph
 from .attractor import attractor, random_spins, consensus_curve
-from .quench import flip_gains, quench, quench_restarts, quench_exchange
+from .quench import flip_gains, quench, quench_restarts, quench_exchange, quench_anneal, anneal_thresholds
 from .census import census, census_minima, attractor_census
 from .sa import SAReplicas, E_delta, sa_run, schedule_constants
 from .sa_er import SAReplicasER, sa_er_run
@@ -34,7 +34,7 @@ __all__ = [
     "MjxError", "lib_path", "BinnedPlan", "neighbour_arrays", "graphs_from_npz", "Graph", "neighbours", "csr_from_networkx", "random_regular_graph",
     "random_regular_edges", "erdos_renyi", "erdos_renyi_device", "erdos_renyi_edges", "csr_from_edges", "remove_isolated",
     "onestep_majority", "s_endstate", "m", "pack", "unpack", "rollout", "popcount", "as_graph",
-    "attractor", "random_spins", "consensus_curve", "flip_gains", "quench", "quench_restarts", "quench_exchange", "census", "census_minima", "attractor_census",
+    "attractor", "random_spins", "consensus_curve", "flip_gains", "quench", "quench_restarts", "quench_exchange", "quench_anneal", "anneal_thresholds", "census", "census_minima", "attractor_census",
     "SAReplicas", "E_delta", "sa_run", "schedule_constants",
     "SAReplicasER", "sa_er_run",
     "HPRPlan", "HPRState", "HPr_dp", "marginals_comp", "new_biases_i", "hpr_run", "hpr_plan_indices",

@@ -162,6 +162,12 @@ SIGNATURES = {
                                      c_vp],
     "mjx_quench_exchange_jobs_csr": [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_vp, c_vp,
                                      c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_quench_anneal_jobs_lds": [c_i64, c_int, c_vp],
+    "mjx_quench_anneal_jobs_ell": [c_vp, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_u64,
+                                   c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp],
+    "mjx_quench_anneal_jobs_csr": [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_u64, c_vp,
+                                   c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_lds": [c_i64],
     "mjx_census_ell": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp],
@@ -180,6 +186,7 @@ _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "
              "mjx_quench_lds": c_i64, "mjx_flip_gain_scratch_bytes": c_i64, "mjx_quench_scratch_bytes": c_i64,
              "mjx_quench_regions_scratch_bytes": c_i64, "mjx_quench_jobs_lds": c_i64,
              "mjx_quench_exchange_jobs_lds": c_i64,
+             "mjx_quench_anneal_jobs_lds": c_i64,
              "mjx_census_lds": c_i64, "mjx_attractor_census_lds": c_i64}
 
 MJX_OK, MJX_EINVAL, MJX_EHIP, MJX_ERANGE = 0, 1, 2, 3      # status codes (include/mjx.h)

@@ -31,7 +31,11 @@ and write its np.savez keys.
         mag_restarts (R, K) and best.  ``--exchange [--max-passes P]`` (with
         ``--restarts K``): the (1, 2) exchange descent behind every job's pass
         (quench.quench_exchange); adds mag_quench, exchanges, passes, converged
-        (R, K).  ``--schedule regions [--window K]``:
+        (R, K).  ``--anneal SWEEPS [--beta B0 B1] [--anneal-seed A]`` (with
+        ``--restarts K``): Metropolis add / drop sweeps inside the consensus
+        set behind every job's pass (quench.quench_anneal); adds mag_quench,
+        mag_best_sweep, best_sweep, adds, drops, refused (R, K).
+        ``--schedule regions [--window K]``:
         the single pass in rounds (same output; quench.quench's schedule)
   census  no reference script: the exact consensus census (census.census) of
         one small random regular or Erdos-Renyi graph (n <= 48, isolated nodes
@@ -136,6 +140,21 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--schedule regions is a schedule of the single pass: not with --exchange")
             if a.max_passes is not None and (not a.exchange or a.max_passes < 1):
                 self.error("--max-passes P (P >= 1) belongs to --exchange")
+            if a.anneal is not None:
+                if a.anneal < 0:
+                    self.error("--anneal SWEEPS must be >= 0")
+                if a.restarts < 1:
+                    self.error("--anneal runs behind the jobs of --restarts K --order-seed S (K >= 1)")
+                if a.exchange:
+                    self.error("--anneal and --exchange are two walks behind the same pass: one of them")
+                if a.schedule == "regions":
+                    self.error("--schedule regions is a schedule of the single pass: not with --anneal")
+                if a.anneal_seed is not None and not 0 <= a.anneal_seed < 2 ** 64:
+                    self.error("--anneal-seed A: 0 <= A < 2^64")
+                if a.beta is not None and (min(a.beta) < 0 or not all(np.isfinite(a.beta))):
+                    self.error("--beta B0 B1: finite inverse temperatures >= 0")
+            elif a.beta is not None or a.anneal_seed is not None:
+                self.error("--beta and --anneal-seed belong to --anneal SWEEPS")
         return a
 
 
@@ -204,6 +223,13 @@ def build_parser():
     qu.add_argument("--max-passes", type=int, default=None,
                     help="--exchange: passes over the order at most (default 8); they end with the first that "
                          "commits nothing")
+    qu.add_argument("--anneal", type=int, default=None, metavar="SWEEPS",
+                    help="with --restarts K: SWEEPS Metropolis sweeps of n add / drop proposals inside the consensus "
+                         "set behind every job's pass, closed by a pass from the lightest sweep end "
+                         "(quench.quench_anneal)")
+    qu.add_argument("--beta", type=float, nargs=2, default=None, metavar=("B0", "B1"),
+                    help="--anneal: inverse temperature from B0 (first sweep) to B1 (last), linear (default 1.5 6.0)")
+    qu.add_argument("--anneal-seed", type=int, default=None, help="--anneal: key of the proposal stream (default 0)")
     qu.add_argument("--schedule", choices=("sequential", "regions"), default="sequential",
                     help="of the single pass (--restarts 0): regions commits candidates whose balls do not meet in "
                          "the same round; same output, faster on large graphs")
@@ -409,12 +435,17 @@ def run_quench(a):
     if a.restarts >= 1:
         # best of K orders per replica, every (replica, order) a job of one call; SA / HPR files: the
         # (R, n, d) stack, a graph per replica
-        from .quench import quench_exchange, quench_restarts
+        from .quench import quench_anneal, quench_exchange, quench_restarts
         g = res["graphs"].astype(np.int32) if "graphs" in res else Graph.csr(res["row_ptr"], res["col"])
         if a.exchange:
             qr = quench_exchange(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed,
                                  max_passes=8 if a.max_passes is None else a.max_passes)
             for key in ("mag_quench", "exchanges", "passes", "converged"):
+                res[key] = qr[key]
+        elif a.anneal is not None:
+            qr = quench_anneal(g, S, a.p, a.c, a.anneal, beta=None if a.beta is None else tuple(a.beta),
+                               restarts=a.restarts, seed=a.order_seed, anneal_seed=a.anneal_seed or 0)
+            for key in ("mag_quench", "mag_best_sweep", "best_sweep", "adds", "drops", "refused"):
                 res[key] = qr[key]
         else:
             qr = quench_restarts(g, S, a.p, a.c, restarts=a.restarts, seed=a.order_seed)

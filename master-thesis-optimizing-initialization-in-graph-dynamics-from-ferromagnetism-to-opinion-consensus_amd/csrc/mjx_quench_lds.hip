@@ -22,6 +22,7 @@
 // they are turned with LDS atomics, whole words are stored by one lane.
 // Everything is integer.
 #include "mjx_quench_parts.h"
+#include "mjx_philox.h"
 #include <algorithm>
 
 namespace mjx {
@@ -32,6 +33,8 @@ constexpr int64_t kQjLdsMax = 64 * 1024;      // the ceiling of mjx_quench.hip: 
 constexpr int QJ_OVERFLOW = 1;                // flag bits of a job
 constexpr int QJ_BAD_INDEX = 2;
 constexpr int QJ_RESTORE = 4;                 // exchange only: a restoring flip did not commit
+constexpr int QJ_ADD = QJ_RESTORE;            // anneal only: an accepted add did not commit; bit 2 on purpose, as
+                                              // QJ_RESTORE: "a flip that must commit did not", one kernel raises one
 constexpr int QX_MAXT = 3;                    // exchange only: the candidate list is a ball of radius 2T <= 6
 
 struct QjPlan {
@@ -175,20 +178,23 @@ __device__ __forceinline__ uint32_t qj_valid(int n, int w) {
 
 // Steps 1-4 of a job: the start into L_0, the T sweeps, the consensus test and the
 // walk over `ord`.  s_np / r: the starts and the job's row of them.  Returns the job's
-// flag (0, QJ_OVERFLOW or QJ_BAD_INDEX).
-template <class Adj>
+// flag (0, QJ_OVERFLOW or QJ_BAD_INDEX).  Load = false: steps 2-4 on the L_0 that is in
+// LDS already (padding bits 0, marks clear); s_np and r are not read.
+template <class Adj, bool Load = true>
 __device__ __forceinline__ int qj_quench_phase(const Adj& A, const QjPlan& P, int n, const uint32_t* __restrict__ s_np,
                                                int64_t r, const int32_t* __restrict__ ord, uint32_t* qj_lds,
                                                bool& cons, long long& nflip) {
     const int lane = threadIdx.x;
     const int T = P.T, W32 = P.W32;
-    uint32_t* mark = qj_lds + (T + 1) * W32;
-    // 1. the start (padding bits 0 whatever the caller left there), marks cleared
-    for (int w = lane; w < W32; w += 64) {
-        qj_lds[w] = s_np[r * W32 + w] & qj_valid(n, w);
-        mark[w] = 0;
+    if constexpr (Load) {
+        uint32_t* mark = qj_lds + (T + 1) * W32;
+        // 1. the start (padding bits 0 whatever the caller left there), marks cleared
+        for (int w = lane; w < W32; w += 64) {
+            qj_lds[w] = s_np[r * W32 + w] & qj_valid(n, w);
+            mark[w] = 0;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     // 2. L_1 .. L_T: 64 nodes at a time, the wave's ballot is their node-packed word
     for (int t = 1; t <= T; ++t) {
         const uint32_t* Lp = qj_lds + (t - 1) * W32;
@@ -478,6 +484,123 @@ k_quench_exchange_jobs(Adj A0, QjPlan P, int xcap, int xoff, int n, int64_t grap
     }
 }
 
+// ---- Metropolis add / drop inside the consensus set (definitions: include/mjx.h) ----
+// what the anneal entry points take on top of the quench ones
+struct QaArgs {
+    int sweeps;
+    const uint32_t* thr;           // device uint32 [sweeps]: an add is accepted when its word is below thr[u]
+    uint64_t seed;
+    int64_t *plus_quench, *plus_best, *best_sweep, *moves;
+    int32_t* trace;                // may be NULL
+};
+
+// +1 spins of bitmap L, wave-uniform
+__device__ __forceinline__ int qa_ones(const uint32_t* L, int W32) {
+    int ones = 0;
+    for (int w = threadIdx.x; w < W32; w += 64) ones += __popc(L[w]);
+    for (int off = 32; off; off >>= 1) ones += __shfl_xor(ones, off);
+    return ones;
+}
+
+// One wave, one job: the quench pass, `sweeps` sweeps of n proposals each, the lightest
+// sweep end kept in a snapshot bitmap behind the job's LDS (word `boff`), and the quench
+// pass again from the snapshot.  Proposal q of sweep u is Philox word 0 (the node) and
+// word 1 (the add's accept test) of counter (q, u, r, k): lane l draws q = base + l, the
+// wave takes the 64 in turn.  A +1 node is one qj_try (a refusal leaves the levels as they
+// were); an accepted add is one qj_try, which commits because the rule is monotone.
+template <class Adj>
+__global__ void __launch_bounds__(64)
+k_quench_anneal_jobs(Adj A0, QjPlan P, int boff, int n, int64_t graph_stride, int K, QaArgs X,
+                     const uint32_t* __restrict__ s_np, const int32_t* __restrict__ order, int64_t order_stride_r,
+                     uint32_t* __restrict__ out_np, long long* __restrict__ flipped, long long* __restrict__ plus,
+                     uint8_t* __restrict__ consensus, int32_t* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t qj_lds[];
+    const int lane = threadIdx.x;
+    const int64_t job = blockIdx.x;
+    const int64_t r = job / K;
+    const int k = (int)(job - r * K);
+    const Adj A = A0.at(r * graph_stride);
+    const int32_t* ord = order + r * order_stride_r + (int64_t)k * n;
+    const int T = P.T, W32 = P.W32, U = X.sweeps;
+    uint32_t* snap = qj_lds + boff;
+    int32_t* trace = X.trace ? X.trace + job * U : nullptr;
+    bool cons;
+    long long nflip;
+    int err = qj_quench_phase(A, P, n, s_np, r, ord, qj_lds, cons, nflip);
+    int ones = qa_ones(qj_lds, W32);                         // the weight, wave-uniform from here on
+    const int ones_q = ones;
+    int ones_best = ones, best_u = 0;
+    long long nadd = 0, ndrop = 0, nref = 0;
+    if (!cons || err) {
+        // no consensus (or a stopped job): the start stays, the trace is flat
+        if (trace)
+            for (int u = lane; u < U; u += 64) trace[u] = ones;
+    } else {
+        for (int w = lane; w < W32; w += 64) snap[w] = qj_lds[w];
+        const uint32_t k0 = (uint32_t)X.seed, k1 = (uint32_t)(X.seed >> 32);
+        for (int u = 0; u < U && !err; ++u) {
+            const uint32_t thr = X.thr[u];
+            for (int base = 0; base < n && !err; base += 64) {
+                uint32_t x[4];
+                philox4x32_10((uint32_t)(base + lane), (uint32_t)u, (uint32_t)r, (uint32_t)k, k0, k1, x);
+                const int node = (int)__umulhi(x[0], (uint32_t)n);          // < n
+                const u64 yes = __ballot(x[1] < thr);
+                const int m_end = min(64, n - base);
+                for (int m = 0; m < m_end; ++m) {
+                    const int i = __builtin_amdgcn_readlane(node, m);
+                    if (qj_bit(qj_lds, i)) {
+                        const int res = T == 0 ? 0 : qj_try(A, P, qj_lds, n, i);   // T = 0: all +1, no drop keeps it
+                        if (res < 0) {
+                            err = -res;
+                            break;
+                        }
+                        ndrop += res;
+                        nref += 1 - res;
+                        ones -= res;
+                    } else if ((yes >> m) & 1) {
+                        const int res = qj_try(A, P, qj_lds, n, i);
+                        if (res != 1) {                      // an add changes nothing at level T
+                            err = res < 0 ? -res : QJ_ADD;
+                            break;
+                        }
+                        ++nadd;
+                        ++ones;
+                    }
+                }
+            }
+            if (err) break;
+            if (trace && lane == 0) trace[u] = ones;
+            if (ones < ones_best) {
+                for (int w = lane; w < W32; w += 64) snap[w] = qj_lds[w];
+                ones_best = ones;
+                best_u = u + 1;
+            }
+        }
+        if (!err) {
+            // the closing pass: the snapshot back into L_0 (the marks are clear after every try)
+            __syncthreads();
+            for (int w = lane; w < W32; w += 64) qj_lds[w] = snap[w];
+            __syncthreads();
+            bool cons2;
+            long long nflip2;
+            err = qj_quench_phase<Adj, false>(A, P, n, nullptr, 0, ord, qj_lds, cons2, nflip2);
+        }
+    }
+    ones = qj_store(qj_lds, W32, out_np, job);
+    if (lane == 0) {
+        flipped[job] = nflip;
+        plus[job] = ones;
+        X.plus_quench[job] = ones_q;
+        X.plus_best[job] = ones_best;
+        X.best_sweep[job] = best_u;
+        X.moves[job * 3 + 0] = nadd;
+        X.moves[job * 3 + 1] = ndrop;
+        X.moves[job * 3 + 2] = nref;
+        flag[job] = err;
+        if (k == 0) consensus[r] = cons ? 1 : 0;
+    }
+}
+
 // bitmaps and list capacities from the caps (HOST int64 [T+1])
 int qj_plan(int64_t n, int T, const int64_t* caps, QjPlan& P) {
     if (T < 0 || T > QJ_MAXT || !caps || n < 1 || n > (int64_t)INT32_MAX) return MJX_EINVAL;
@@ -517,11 +640,18 @@ int qx_plan(int64_t n, int T, const int64_t* caps, int64_t cap2T, QjPlan& P, int
     return bytes > kQjLdsMax ? MJX_EINVAL : MJX_OK;
 }
 
+// the anneal's LDS: the quench job's, then the snapshot bitmap
+int qa_plan(int64_t n, int T, const int64_t* caps, QjPlan& P, int64_t& bytes) {
+    if (int rc = qj_plan(n, T, caps, P)) return rc;
+    bytes = (P.bytes + 4 * (int64_t)P.W32 + 15) / 16 * 16;
+    return bytes > kQjLdsMax ? MJX_EINVAL : MJX_OK;
+}
+
 template <class Adj>
 int quench_jobs_run(Adj A, int64_t n, int64_t graph_stride, int64_t R, int64_t K, int p, int c, const int64_t* caps,
                     const uint64_t* s_np, const int32_t* order, int64_t order_stride_r, uint64_t* out_np,
                     int64_t* flipped, int64_t* plus, uint8_t* consensus, int32_t* flag, void* stream,
-                    const QxArgs* X = nullptr) {
+                    const QxArgs* X = nullptr, const QaArgs* Y = nullptr) {
     const int T = p + c - 1;
     if (p < 0 || c < 0 || R < 1 || K < 1 || K > (int64_t)INT32_MAX || R * K > (int64_t)INT32_MAX || !s_np || !order ||
         !out_np || !flipped || !plus || !consensus || !flag)
@@ -540,6 +670,18 @@ int quench_jobs_run(Adj A, int64_t n, int64_t graph_stride, int64_t R, int64_t K
             (long long*)X->plus_quench, (long long*)X->exchanges, (long long*)X->passes, X->converged, consensus, flag,
             (long long*)X->stats);
         MJX_LAUNCH_CHECK("k_quench_exchange_jobs");
+        return MJX_OK;
+    }
+    if (Y) {
+        if (Y->sweeps < 0 || (Y->sweeps > 0 && !Y->thr) || !Y->plus_quench || !Y->plus_best || !Y->best_sweep ||
+            !Y->moves)
+            return MJX_EINVAL;
+        int64_t bytes;
+        if (int rc = qa_plan(n, T, caps, P, bytes)) return rc;
+        k_quench_anneal_jobs<Adj><<<(unsigned)(R * K), 64, (size_t)bytes, as_stream(stream)>>>(
+            A, P, (int)(P.bytes / 4), (int)n, graph_stride, (int)K, *Y, (const uint32_t*)s_np, order, order_stride_r,
+            (uint32_t*)out_np, (long long*)flipped, (long long*)plus, consensus, flag);
+        MJX_LAUNCH_CHECK("k_quench_anneal_jobs");
         return MJX_OK;
     }
     if (int rc = qj_plan(n, T, caps, P)) return rc;
@@ -609,4 +751,38 @@ extern "C" int mjx_quench_exchange_jobs_csr(const int64_t* row_ptr, const int32_
     const QxArgs X{cap2T, max_passes, rank_work, plus_quench, exchanges, passes, converged, stats};
     return quench_jobs_run(AdjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
                            plus, consensus, flag, stream, &X);
+}
+
+extern "C" int64_t mjx_quench_anneal_jobs_lds(int64_t n, int T, const int64_t* caps) {
+    QjPlan P;
+    int64_t bytes;
+    return qa_plan(n, T, caps, P, bytes) ? -1 : bytes;
+}
+
+extern "C" int mjx_quench_anneal_jobs_ell(const int32_t* adj, int64_t n, int d, int64_t graph_stride, int64_t R,
+                                          int64_t K, int p, int c, const int64_t* caps, int64_t sweeps,
+                                          const uint32_t* thr, uint64_t seed, const uint64_t* s_np,
+                                          const int32_t* order, int64_t order_stride_r, uint64_t* out_np,
+                                          int64_t* flipped, int64_t* plus, int64_t* plus_quench, int64_t* plus_best,
+                                          int64_t* best_sweep, int64_t* moves, int32_t* trace, uint8_t* consensus,
+                                          int32_t* flag, void* stream) {
+    if (!adj_ell_ok(adj, d) || (graph_stride != 0 && graph_stride != n * d) || sweeps < 0 ||
+        sweeps > (int64_t)INT32_MAX)
+        return MJX_EINVAL;
+    const QaArgs Y{(int)sweeps, thr, seed, plus_quench, plus_best, best_sweep, moves, trace};
+    return quench_jobs_run(AdjEll{adj, d}, n, graph_stride, R, K, p, c, caps, s_np, order, order_stride_r, out_np,
+                           flipped, plus, consensus, flag, stream, nullptr, &Y);
+}
+
+extern "C" int mjx_quench_anneal_jobs_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int64_t R, int64_t K,
+                                          int p, int c, const int64_t* caps, int64_t sweeps, const uint32_t* thr,
+                                          uint64_t seed, const uint64_t* s_np, const int32_t* order,
+                                          int64_t order_stride_r, uint64_t* out_np, int64_t* flipped, int64_t* plus,
+                                          int64_t* plus_quench, int64_t* plus_best, int64_t* best_sweep,
+                                          int64_t* moves, int32_t* trace, uint8_t* consensus, int32_t* flag,
+                                          void* stream) {
+    if (!adj_csr_ok(row_ptr) || sweeps < 0 || sweeps > (int64_t)INT32_MAX) return MJX_EINVAL;
+    const QaArgs Y{(int)sweeps, thr, seed, plus_quench, plus_best, best_sweep, moves, trace};
+    return quench_jobs_run(AdjCsr{row_ptr, col}, n, 0, R, K, p, c, caps, s_np, order, order_stride_r, out_np, flipped,
+                           plus, consensus, flag, stream, nullptr, &Y);
 }

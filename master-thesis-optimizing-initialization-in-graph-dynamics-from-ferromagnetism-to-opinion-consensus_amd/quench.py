@@ -475,13 +475,15 @@ def _host_shapes(graph, s):
     return stack, n, R
 
 
-def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t, exchange=None, what="quench_restarts"):
+def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t, exchange=None, what="quench_restarts", anneal=None):
     """The device call: R x K jobs -> (out_np int64 (R K, ceil(n/64)), flipped int64 [R K], plus int64 [R K],
     consensus uint8 [R]).  g: the shared graph, or any graph of ``adj_stack`` (device int32 (R, n, d): a graph
     per start); s_np int64 (R, ceil(n/64)); order_t device int32 (1 or R, K, n).  ``exchange`` = (cap2T,
     max_passes, "with stats"): the exchange descent behind the pass (mjx_quench_exchange_jobs_*); a fifth
     entry of the result then holds plus_quench, exchanges, passes int64 [R K], converged uint8 [R K] and
-    stats int64 (R K, 4) or None."""
+    stats int64 (R K, 4) or None.  ``anneal`` = (thr device int32 tensor holding the uint32 thresholds, seed,
+    "with trace"): the Metropolis sweeps behind the pass (mjx_quench_anneal_jobs_*); the fifth entry then holds
+    plus_quench, plus_best, best_sweep int64 [R K], moves int64 (R K, 3) and trace int32 (R K, U) or None."""
     n, dev, st = g.n, s_np.device, _device.stream_handle()
     Wn = (n + 63) // 64
 
@@ -494,7 +496,16 @@ def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t, exchange=None, what
     starts = (_device.ptr(s_np), _device.ptr(order_t), K * n if order_t.shape[0] > 1 else 0)
     outs = (_device.ptr(out_np), _device.ptr(flipped), _device.ptr(plus))
     ends = (_device.ptr(consensus), _device.ptr(flag))
-    if exchange is None:
+    if anneal is not None:
+        thr, seed, with_trace = anneal
+        U = int(thr.numel())
+        more = {"plus_quench": new(torch.int64), "plus_best": new(torch.int64), "best_sweep": new(torch.int64),
+                "moves": new(torch.int64, R * K, 3), "trace": new(torch.int32, R * K, U) if with_trace else None}
+        entry = "mjx_quench_anneal_jobs"
+        tail = (*jobs, U, _device.ptr(thr) if U else None, seed, *starts, *outs, _device.ptr(more["plus_quench"]),
+                _device.ptr(more["plus_best"]), _device.ptr(more["best_sweep"]), _device.ptr(more["moves"]),
+                _device.ptr(more["trace"]) if with_trace and U else None, *ends, st)
+    elif exchange is None:
         entry, tail, more = "mjx_quench_jobs", (*jobs, *starts, *outs, *ends, st), None
     else:
         cap2T, max_passes, with_stats = exchange
@@ -516,18 +527,20 @@ def _run_jobs(g, adj_stack, R, K, p, c, caps, s_np, order_t, exchange=None, what
     if flags & 2:
         raise _lib.MjxError(f"{what}: an order or adjacency entry lies outside 0..n-1")
     if flags:
-        raise _lib.MjxError(f"{what}: a flip that restores the state did not commit (a bug in the kernel)")
+        raise _lib.MjxError(f"{what}: " + ("an accepted add" if anneal is not None else "a flip that restores the state")
+                            + " did not commit (a bug in the kernel)")
     res = (out_np, flipped, plus, consensus)
-    return res if exchange is None else res + (more,)
+    return res if more is None else res + (more,)
 
 
 EXCHANGE_T_MAX = 3          # the candidates of an add lie in a ball of radius 2T, and the ball bounds serve 6
 
 
 def _quench_jobs(what, graph, s, p, c, restarts, orders, seed, keep_all, kernel, validate, exchange=False,
-                 max_passes=None):
-    """``quench_restarts`` and ``quench_exchange`` (``exchange``, with its ``max_passes``): the checks, the
-    device call and the result dict they share."""
+                 max_passes=None, anneal=None):
+    """``quench_restarts``, ``quench_exchange`` (``exchange``, with its ``max_passes``) and ``quench_anneal``
+    (``anneal`` = (uint32 numpy thresholds, seed, "with trace")): the checks, the device call and the result
+    dict they share."""
     p, c, T = _steps(p, c)
     if kernel:
         raise ValueError(f"unknown kernel options {sorted(dict(kernel))}")
@@ -546,6 +559,7 @@ def _quench_jobs(what, graph, s, p, c, restarts, orders, seed, keep_all, kernel,
     def lds_of(caps, caps2):
         """LDS bytes of a job; refuses a shape that does not fit."""
         lds = int(lib.mjx_quench_exchange_jobs_lds(n, T, caps, caps2[2 * T]) if exchange else
+                  lib.mjx_quench_anneal_jobs_lds(n, T, caps) if anneal is not None else
                   lib.mjx_quench_jobs_lds(n, T, caps))
         if lds < 0:
             raise ValueError(f"{what}: a job of n = {n}, p + c - 1 = {T} (ball bound {list(caps)}) does not fit "
@@ -588,9 +602,12 @@ def _quench_jobs(what, graph, s, p, c, restarts, orders, seed, keep_all, kernel,
     for r in range(R):
         _lib.call("mjx_pack_np", t.data_ptr() + r * step, code, n, s_np.data_ptr() + r * Wn * 8, st)
     order_t = _device.to_device(orders)
+    if anneal is not None:
+        # the uint32 thresholds travel as the same bits in an int32 tensor
+        anneal = (_device.to_device(anneal[0].view(np.int32)), anneal[1], anneal[2])
     out_np, flipped, plus, consensus, *more = _run_jobs(
         g, adj_t if stack else None, R, K, p, c, caps, s_np, order_t,
-        (int(caps2[2 * T]), max_passes, False) if exchange else None, what)
+        (int(caps2[2 * T]), max_passes, False) if exchange else None, what, anneal)
     sums = 2 * plus.cpu().numpy().reshape(R, K) - n
     best = pick_best(sums)
     # sum(s) / n as numpy divides two integers, as quench does
@@ -615,6 +632,15 @@ def _quench_jobs(what, graph, s, p, c, restarts, orders, seed, keep_all, kernel,
         out.update({"mag_quench": _like(torch.from_numpy(mag_quench), s),
                     "exchanges": _like(x["exchanges"].view(R, K), s), "passes": _like(x["passes"].view(R, K), s),
                     "converged": _like(x["converged"].view(R, K).to(torch.bool), s)})
+    if anneal is not None:
+        x = more[0]
+        for key, src in (("mag_quench", "plus_quench"), ("mag_best_sweep", "plus_best")):
+            out[key] = _like(torch.from_numpy((2 * x[src].cpu().numpy().reshape(R, K) - n) / n), s)
+        out["best_sweep"] = _like(x["best_sweep"].view(R, K), s)
+        for j, key in enumerate(("adds", "drops", "refused")):
+            out[key] = _like(x["moves"][:, j].contiguous().view(R, K), s)
+        if anneal[2]:
+            out["trace"] = _like(x["trace"].view(R, K, -1), s)
     if keep_all:
         out["conf"] = _like(rows(out_np, torch.int8).view(R, K, n), s)
     return out
@@ -669,3 +695,84 @@ def quench_exchange(graph, s, p, c, restarts=1, orders=None, seed=None, max_pass
     consensus) and ``converged`` bool (the last pass committed nothing)."""
     return _quench_jobs("quench_exchange", graph, s, p, c, restarts, orders, seed, keep_all, kernel, validate,
                         exchange=True, max_passes=max_passes)
+
+
+ANNEAL_BETA = (1.5, 6.0)     # quench_anneal's ``beta`` when neither beta nor thresholds is given
+
+
+def anneal_thresholds(beta):
+    """Inverse temperatures -> the uint32 accept thresholds of ``quench_anneal``:
+    min(floor(exp(-beta) * 2^32), 2^32 - 1) in float64, so an add whose 32-bit
+    word lies below the threshold is accepted with probability e^{-beta} (to
+    2^-32).  beta = 0 gives 2^32 - 1, ``inf`` gives 0; a negative or NaN beta
+    is refused.  Host only."""
+    b = np.atleast_1d(np.asarray(beta, dtype=np.float64))
+    if b.ndim != 1 or np.isnan(b).any() or (b < 0).any():
+        raise ValueError("beta must be a vector of inverse temperatures >= 0")
+    return np.minimum(np.floor(np.exp(-b) * 4294967296.0), 4294967295.0).astype(np.uint32)
+
+
+def _check_anneal(sweeps, beta, thresholds, anneal_seed):
+    """Host only -> (uint32 numpy thresholds [sweeps], seed in 0 .. 2^64 - 1)."""
+    if not isinstance(sweeps, (int, np.integer)) or isinstance(sweeps, bool) or not 0 <= sweeps < 2 ** 31:
+        raise ValueError(f"sweeps must be an integer in 0 .. 2^31 - 1, got {sweeps!r}")
+    U = int(sweeps)
+    if thresholds is not None:
+        if beta is not None:
+            raise ValueError("give beta or thresholds, not both")
+        thr = np.asarray(thresholds.cpu() if isinstance(thresholds, torch.Tensor) else thresholds)
+        if thr.shape != (U,) or not np.issubdtype(thr.dtype, np.integer) or \
+                (U and (int(thr.min()) < 0 or int(thr.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"thresholds must be {U} integers in 0 .. 2^32 - 1, one per sweep")
+        thr = thr.astype(np.uint32)
+    else:
+        b = np.asarray(ANNEAL_BETA if beta is None else beta, dtype=np.float64)
+        if b.shape == (2,) and U != 2:                      # U = 2: the pair and the array are the same thing
+            if not np.isfinite(b).all():
+                raise ValueError("beta as a pair (first, last) must be finite: np.linspace(first, last, sweeps)")
+            b = np.linspace(b[0], b[1], U)
+        elif b.shape != (U,):
+            raise ValueError(f"beta must be a pair (first, last) or an array of sweeps = {U} values")
+        thr = anneal_thresholds(b) if U else np.zeros(0, np.uint32)
+    if not isinstance(anneal_seed, (int, np.integer)) or isinstance(anneal_seed, bool) or \
+            not 0 <= int(anneal_seed) < 2 ** 64:
+        raise ValueError(f"anneal_seed must be an integer in 0 .. 2^64 - 1, got {anneal_seed!r}")
+    return np.ascontiguousarray(thr), int(anneal_seed)
+
+
+def quench_anneal(graph, s, p, c, sweeps, beta=None, thresholds=None, restarts=1, orders=None, seed=None,
+                  anneal_seed=0, trace=False, keep_all=False, validate=True):
+    """``quench_restarts`` with a Metropolis walk inside the consensus set behind
+    every job's pass: simulated annealing on the weight that never leaves
+    consensus.
+
+    After its quench pass a job makes ``sweeps`` sweeps of n proposals.  A
+    proposal draws a node (Philox, keyed by ``anneal_seed``, counter (proposal,
+    sweep, start r, restart k), so a job's stream does not depend on R or K):
+    a +1 node is dropped when consensus survives (always: it lowers the
+    weight), a -1 node is added with probability e^{-beta} of the sweep (an add
+    cannot leave consensus).  The lightest state seen at a sweep end is kept,
+    and the job closes with a quench pass from it, so the result is a consensus
+    single-flip local minimum and never heavier than ``quench_restarts``' on
+    the same job; ``sweeps = 0`` is exactly ``quench_restarts``.  include/mjx.h
+    has the definition; results are integer-exact functions of the inputs.
+
+    ``beta``: a pair (first, last), meaning ``np.linspace(first, last,
+    sweeps)``, or an array of ``sweeps`` inverse temperatures >= 0 (``inf``:
+    no add; the pair must be finite, ``np.linspace`` has to reach its end);
+    default ``None`` = (1.5, 6.0), which comes from CPU runs at n <= 96 and has
+    NOT been tuned at n = 1e4.  ``thresholds``: instead of ``beta``, the uint32
+    accept thresholds themselves (``anneal_thresholds``); giving both raises
+    ValueError.  Inputs, orders / ``seed`` rule (``seed`` is the ORDER seed),
+    graph forms and refusals as ``quench_restarts``; p + c - 1 <= 6.
+
+    Returns ``quench_restarts``' dict (``mag``, ``best``, ``conf_best``, ...
+    describe the final states; ``flipped`` the first pass) plus, all (R, K):
+    ``mag_quench`` float64 (sum(s)/n after the first pass), ``mag_best_sweep``
+    float64 (of the lightest sweep end, before the closing pass),
+    ``best_sweep`` int64 (0: no sweep end beat the first pass), ``adds``,
+    ``drops``, ``refused`` int64, and with ``trace=True`` ``trace`` int32
+    (R, K, sweeps), the +1 spins after every sweep."""
+    thr, aseed = _check_anneal(sweeps, beta, thresholds, anneal_seed)
+    return _quench_jobs("quench_anneal", graph, s, p, c, restarts, orders, seed, keep_all, None, validate,
+                        anneal=(thr, aseed, bool(trace)))
