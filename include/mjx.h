@@ -740,6 +740,14 @@ int mjx_bdcm_node_z(const double* chi, const int32_t* nodes, const int32_t* inc,
  * edges[2E] = G.edges (u, v) pairs, deg[n] node degrees; m_term nullable. */
 int mjx_bdcm_edge_obs(const double* chi, const int32_t* edges, const int32_t* deg, int64_t E, int p, int c,
                       int attr_value, double eps, double* zij, double* m_term, void* stream);
+/* The two endpoint terms of that per-edge term apart, for edge e = (u, v) with
+ * its messages at rows e and e + E: m_uv[2e] = <s_u(0)>_e and m_uv[2e+1] =
+ * <s_v(0)>_e, the initial spins averaged under chi^uv chi^vu / max(Zij, eps).
+ * m_term[e] of mjx_bdcm_edge_obs is m_uv[2e] / deg[u] + m_uv[2e+1] / deg[v]; a
+ * node's magnetisation <s_i(0)> is the mean of its terms over its edges.
+ * m_uv: device [2E].  MJX_EINVAL as for mjx_bdcm_edge_obs. */
+int mjx_bdcm_edge_m(const double* chi, int64_t E, int p, int c, int attr_value, double eps, double* m_uv,
+                    void* stream);
 /* out[0] = sum_i x[i] (take_log: sum_i log x[i]), deterministic order;
  * work: 256 doubles of device scratch. */
 int mjx_sum_f64(const double* x, int64_t n, int take_log, double* work, double* out, void* stream);
@@ -1139,6 +1147,44 @@ int mjx_census_ell(const int32_t* adj, int64_t n, int d, int p, int c, int64_t b
 int mjx_census_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int64_t block_lo,
                    int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
                    int32_t* flag, void* stream);
+
+/* ---- census marginals: the counts of one level per node -------------------- */
+/*
+ * mjx_census_nodes_ell / _csr: mjx_census_ell / _csr (same enumeration, counts,
+ * witness keys, flag and status codes) that also counts the configurations of
+ * ONE level t_node, 0 <= t_node <= T, per +1 node:
+ *   Node counts: node_counts[k][v] = #{x : k(x) = k, bit v of x set and
+ *     onestep^t_node(x) is all +1}, (n+1, n).  So sum_v node_counts[k][v] =
+ *     k counts[t_node][k], node_counts <= counts[t_node], and at t_node = 0 the
+ *     row k = n is all ones and the rest 0.
+ *   Backbone: with k* = min_plus[t_node], node v is +1 in every optimal
+ *     configuration iff node_counts[k*][v] = counts[t_node][k*] and -1 in every
+ *     one iff node_counts[k*][v] = 0.
+ * The workgroup keeps node[n+1][n] as 32-bit LDS cells behind its counts and
+ * keys and flushes them with 64-bit global atomics at the end; a launch covers
+ * at most 2^25 blocks (2^31 configurations), so no cell can wrap.  The word of
+ * a lane's block is binned by weight as for the counts; node v < 6 takes the
+ * positions of its level-0 pattern, node v >= 6 the whole word where bit v-6 of
+ * b is set.  In a row of 64 blocks that starts at a multiple of 64 the bits
+ * v >= 12 are the same in every lane: the wave's words are summed by weight
+ * once and lane l adds the sums for node 12 + l.  mjx_census_nodes_lds(n) =
+ *   mjx_census_lds(n) + 4 (n + 1) n
+ * bytes (-1 for n outside 1..48; 64,104 at n = 48, no dynamic-LDS opt-in).
+ *
+ * node_counts: device [n+1][n], ADDED to (64-bit atomics), like counts: [0, B)
+ * may be split over launches into the same buffers.  When the flag comes back
+ * set, nothing has been counted.  MJX_ERANGE: as for mjx_census_*, and
+ * block_hi - block_lo > 2^25.  MJX_EINVAL: as for mjx_census_*, and t_node
+ * outside 0..T.  No allocation, no host synchronisation.
+ */
+int64_t mjx_census_nodes_lds(int64_t n);
+int mjx_census_nodes_ell(const int32_t* adj, int64_t n, int d, int p, int c, int t_node, int64_t block_lo,
+                         int64_t block_hi, int grid, unsigned long long* counts, unsigned long long* witness_key,
+                         unsigned long long* node_counts, int32_t* flag, void* stream);
+int mjx_census_nodes_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int t_node,
+                         int64_t block_lo, int64_t block_hi, int grid, unsigned long long* counts,
+                         unsigned long long* witness_key, unsigned long long* node_counts, int32_t* flag,
+                         void* stream);
 
 /* ---- census of the minimal consensus sets -------------------------------- */
 /*

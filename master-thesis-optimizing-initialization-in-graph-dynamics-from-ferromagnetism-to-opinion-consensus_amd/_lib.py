@@ -127,6 +127,7 @@ SIGNATURES = {
     "mjx_bdcm_node_z": [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_vp, c_vp, c_i64,
                         c_vp],
     "mjx_bdcm_edge_obs": [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_vp, c_vp, c_vp],
+    "mjx_bdcm_edge_m": [c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_vp, c_vp],
     "mjx_sum_f64": [c_vp, c_i64, c_int, c_vp, c_vp, c_vp],
     "mjx_bdcm_update_class_batch": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl,
                                     c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp],
@@ -174,6 +175,9 @@ SIGNATURES = {
     "mjx_census_mask_ell": [c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_mask_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_census_minima": [c_vp, c_i64, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp],
+    "mjx_census_nodes_lds": [c_i64],
+    "mjx_census_nodes_ell": [c_vp, c_i64, c_int, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mjx_census_nodes_csr": [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_attractor_census_lds": [c_i64, c_int],
     "mjx_attractor_census_ell": [c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "mjx_attractor_census_csr": [c_vp, c_vp, c_i64, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
@@ -187,7 +191,7 @@ _RESTYPES = {"mjx_strerror": ctypes.c_char_p, "mjx_build_id": ctypes.c_char_p, "
              "mjx_quench_regions_scratch_bytes": c_i64, "mjx_quench_jobs_lds": c_i64,
              "mjx_quench_exchange_jobs_lds": c_i64,
              "mjx_quench_anneal_jobs_lds": c_i64,
-             "mjx_census_lds": c_i64, "mjx_attractor_census_lds": c_i64}
+             "mjx_census_lds": c_i64, "mjx_attractor_census_lds": c_i64, "mjx_census_nodes_lds": c_i64}
 
 MJX_OK, MJX_EINVAL, MJX_EHIP, MJX_ERANGE = 0, 1, 2, 3      # status codes (include/mjx.h)
 MJX_I8, MJX_I32, MJX_I64 = 1, 4, 8

@@ -338,6 +338,21 @@ def avg_m_init_GENERAL_ER(chi, plan, p, c, attr_value, epsilon=0.0):
     return observables(chi, plan, p, c, attr_value, 0.0, epsilon)[1]
 
 
+def bdcm_node_m_init(chi, plan, p, c, attr_value, epsilon=0.0):
+    """(n_core,) float64 device tensor: the initial magnetisation <s_i(0)> of
+    every core node, the mean over its edges of the edge's own estimate
+    (mjx_bdcm_edge_m) -- the per-node terms whose sum ``avg_m_init_GENERAL_ER``
+    takes edge by edge: (sum + attr_value n_iso) / n is that average.  Exact on
+    a tree at the fixed point, where every edge of a node gives the same value."""
+    ch = _chi2d(chi, plan, p, c)
+    m_uv = torch.empty(2 * plan.E, dtype=torch.float64, device=ch.device)
+    _lib.call("mjx_bdcm_edge_m", _device.ptr(ch), plan.E, int(p), int(c), int(attr_value), float(epsilon),
+              _device.ptr(m_uv), _device.stream_handle())
+    # plan.edges is (u, v) per edge, flat: the layout of m_uv
+    total = torch.zeros(plan.n_core, dtype=torch.float64, device=ch.device).index_add_(0, plan.edges.long(), m_uv)
+    return total / plan.deg.to(torch.float64)
+
+
 def BDCM_entropy_procedure_GENERAL_ER(chi, plan, lambdas, T_max=1300, p=1, c=1, attr_value=1, eps=1e-6,
                                       damppar=0.1, epsilon=0.0, stop_ent=-0.05, verbose=False, device_loop=True,
                                       batch=32):

@@ -24,6 +24,10 @@ how many starts of each weight end all +1, all -1, in another fixed point or in
 a 2-cycle, and after how many steps -- the exact counterpart of
 ``consensus_curve``.
 
+``census_marginals`` counts the configurations of a level per +1 node as well,
+which gives the backbone of the optimum and, through ``census_boltzmann``, the
+exact phi, m_init and per-node marginals that BDCM and BP approximate.
+
 Not covered: several devices (the block range makes it a host loop), n > 48,
 symmetry reduction.  There is no CPU fallback.
 """
@@ -243,6 +247,126 @@ def census_minima(graph, p, c, *, max_configs=2 ** 34, chunk_blocks=None, kernel
     if return_mask:
         res["mask"] = mask
     return res
+
+
+def census_nodes_lds(n):
+    """LDS bytes of a workgroup of the census that also counts per node (mjx_census_nodes_lds without its
+    ceiling): two levels, counts and keys, node[n+1][n] as 32-bit cells, level-0 patterns, row offsets,
+    neighbour bytes."""
+    return (1024 * n + 56 * (n + 2) + 4 * (n + 1) * n + 8 * n + 8 * (-(-(n + 1) // 4))
+            + 8 * (-(-(DEG_MAX * n) // 8)))
+
+
+def _run_nodes(g, p, c, t_node, block_lo, block_hi, chunk, grid):
+    """``_run`` through the entry points that also count level ``t_node`` per node -> (counts, keys, node
+    counts int64 (n+1, n)), device tensors."""
+    n, T = g.n, p + c - 1
+    counts = torch.zeros((T + 1, n + 1), dtype=torch.int64, device=g.device)
+    keys = torch.full((T + 1,), -1, dtype=torch.int64, device=g.device)      # all ones
+    node = torch.zeros((n + 1, n), dtype=torch.int64, device=g.device)
+    _launch("census_nodes", g, (p, c, t_node), block_lo, block_hi, min(chunk, LAUNCH_BLOCKS_MAX), grid,
+            (counts, keys, node), (), "census_marginals")
+    return counts, keys, node
+
+
+def _marginal_levels(levels, T):
+    """``levels`` of ``census_marginals`` -> a list of step counts in 0..T, default [T]."""
+    out = [T] if levels is None else list(levels)
+    if not out:
+        raise ValueError("census_marginals: levels is empty")
+    for t in out:
+        if int(t) != t or not 0 <= t <= T:
+            raise ValueError(f"census_marginals: level {t} is outside 0..T = p + c - 1 = {T}")
+    return [int(t) for t in out]
+
+
+def census_marginals(graph, p, c, *, levels=None, max_configs=2 ** 36, chunk_blocks=None, kernel=None):
+    """``census`` and, for each requested level t, where the +1 spins of the
+    counted configurations sit:
+
+        node_counts[l, k, v] = #{x : popcount(x) = k, bit v of x set,
+                                 onestep^t(x) all +1},  t = levels[l]
+
+    the exact per-node counts that BP marginals and BDCM's m_init approximate
+    (``census_boltzmann`` turns them into the Boltzmann averages at any lambda).
+
+    Arguments and refusals as for ``census``.  ``levels``: step counts in 0..T,
+    T = p + c - 1, default ``[T]``; each is one enumeration by the census kernel
+    with node cells in LDS (mjx_census_nodes_*, include/mjx.h), in launches of
+    at most ``chunk_blocks`` blocks (at most 2^25 take effect).  BDCM at (p, c)
+    corresponds to level t = p: for c = 2, x(p+1) all +1 and x(p+2) = x(p)
+    force x(p) all +1.
+
+    Returns the dict of ``census`` (same values) and ``levels`` (list),
+    ``node_counts`` int64 (len(levels), n+1, n), ``optimal`` int64
+    (len(levels),) = counts[t, min_plus[t]], and the backbone of the optimum,
+    bool (len(levels), n): ``backbone_plus[l, v]`` -- node v is +1 in every
+    configuration of weight min_plus[t] counted at level t
+    (node_counts[l, min_plus[t], v] == optimal[l]) -- and ``backbone_minus``
+    (that node count is 0)."""
+    p_, c_, T = _steps(p, c)
+    lv = _marginal_levels(levels, T)
+
+    def fits(n):
+        lds = census_nodes_lds(n)
+        if lds > LDS_MAX:
+            raise ValueError(f"census_marginals: n = {n} needs {lds} bytes of LDS per workgroup, more than {LDS_MAX}")
+
+    g, n, blocks, chunk, grid = _checked_enumeration(graph, max_configs, chunk_blocks, kernel, fits=fits)
+    runs = [_run_nodes(g, p_, c_, t, 0, blocks, chunk, grid) for t in lv]   # every pass counts the levels anew
+    counts, keys = runs[-1][:2]
+    node = torch.stack([r[2] for r in runs])
+    key = keys.cpu().numpy().view(np.uint64)
+    if (key == np.uint64(0xFFFFFFFFFFFFFFFF)).any():                        # every level counts all +1 at least
+        raise _lib.MjxError("census_marginals: a level without a witness")
+    res = _levels(counts.cpu().numpy(), key, n)
+    nc = node.cpu().numpy()
+    best = res["min_plus"][lv]
+    optimal = res["counts"][lv, best]
+    at_best = nc[np.arange(len(lv)), best]                                  # (len(levels), n)
+    res.update(levels=lv, node_counts=nc, optimal=optimal, backbone_plus=at_best == optimal[:, None],
+               backbone_minus=at_best == 0)
+    return res
+
+
+def census_boltzmann(res, lam, level=-1, attr_value=1):
+    """The exact Boltzmann averages that BDCM approximates, from the counts of
+    ``census_marginals``; float64 numpy, no device.
+
+    With w_k = exp(-lam (2k - n)), t = res["levels"][level] and
+    Z = sum_k counts[t, k] w_k (by log-sum-exp): ``phi`` = ln Z / n, ``m_init``
+    = <2k - n> / n, ``ent1`` = phi + lam m_init, ``p_plus`` (n,) =
+    sum_k node_counts[level, k, v] w_k / Z = P(s_v(0) = +1) and ``m_node`` =
+    2 p_plus - 1.  These are BDCM's definitions (``phi_BP_GENERAL_ER``,
+    ``avg_m_init_GENERAL_ER``) at attractor +1, its isolated nodes included: a
+    node of degree 0 never moves, so it starts +1 in every counted x.
+    ``level`` indexes ``res["levels"]``.  ``lam``: a scalar, or an array -- the
+    outputs then gain a leading axis.  ``attr_value`` = -1 is refused: the
+    census counts the configurations that end all +1 only."""
+    if int(attr_value) != 1:
+        raise ValueError(f"census_boltzmann: attr_value = {attr_value}; the census counts all +1 only (attr_value = 1)")
+    levels = list(res["levels"])
+    if not -len(levels) <= int(level) < len(levels):
+        raise ValueError(f"census_boltzmann: level index {level} is outside the {len(levels)} levels of the result")
+    t = levels[int(level)]
+    counts = np.asarray(res["counts"])[t].astype(np.float64)
+    node = np.asarray(res["node_counts"])[int(level)].astype(np.float64)   # (n+1, n)
+    n = node.shape[1]
+    lam_a = np.asarray(lam, dtype=np.float64)
+    lm = lam_a.reshape(-1)
+    mag = 2.0 * np.arange(n + 1) - n                                       # 2k - n
+    with np.errstate(divide="ignore"):
+        a = np.log(counts)[None, :] - lm[:, None] * mag[None, :]           # ln(counts w_k), -inf where 0
+    top = a.max(axis=1)                                                    # finite: all +1 is counted
+    e = np.exp(a - top[:, None])
+    z = e.sum(axis=1)
+    phi = (top + np.log(z)) / n
+    m_init = (e * mag[None, :]).sum(axis=1) / z / n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = np.where(counts[:, None] > 0, node / counts[:, None], 0.0)  # of the level's weight-k set
+    p_plus = ((e / z[:, None])[:, :, None] * share[None, :, :]).sum(axis=1)  # no BLAS: the same for any batch
+    out = {"phi": phi, "m_init": m_init, "ent1": phi + lm * m_init, "p_plus": p_plus, "m_node": 2.0 * p_plus - 1.0}
+    return {k: v.reshape(lam_a.shape + v.shape[1:]) for k, v in out.items()}
 
 
 def attractor_census_lds(n, t_max):

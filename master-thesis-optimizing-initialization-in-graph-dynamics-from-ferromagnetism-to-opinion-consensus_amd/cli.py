@@ -43,7 +43,12 @@ and write its np.savez keys.
         "census_{graph}.npz": counts, min_plus, m_min, witness, entropy,
         configs, edges.  ``--minima`` adds the census of the minimal consensus
         sets, the local minima of the quenches (census.census_minima): minima,
-        minima_total, max_plus, m_max, witness_max, mean_plus
+        minima_total, max_plus, m_max, witness_max, mean_plus.
+        ``--marginals [--levels T ...] [--lam L ...]`` counts the levels per
+        +1 node instead (census.census_marginals): levels, node_counts, optimal,
+        backbone_plus, backbone_minus and, with ``--lam``, the exact Boltzmann
+        averages of every level and lambda (census.census_boltzmann): lam,
+        phi, m_init, ent1 (levels, lambdas), p_plus, m_node (levels, lambdas, n)
   attractor-census  no reference script: the attractor census
         (census.attractor_census) of one such graph, every one of the 2^n
         starts run until s(t+2) = s(t) (at most t_max + 2 steps); output
@@ -251,6 +256,13 @@ def build_parser():
                          "bytes)")
     ce.add_argument("--minima", action="store_true",
                     help="also count the minimal consensus sets of every level, the local minima of the quenches")
+    ce.add_argument("--marginals", action="store_true",
+                    help="also count the configurations of the levels per +1 node: node counts and the backbone of "
+                         "the optimum")
+    ce.add_argument("--levels", type=int, nargs="+", default=None,
+                    help="--marginals: the step counts to count per node (default: p + c - 1), one enumeration each")
+    ce.add_argument("--lam", type=float, nargs="+", default=None,
+                    help="--marginals: also the exact phi, m_init, ent1 and node marginals at these lambdas")
     ce.add_argument("--out", default=None, help="output .npz (default: census_{graph}.npz)")
     ac = sub.add_parser("attractor-census", help="run all 2^n starts of a small graph to their attractors and count "
                                                  "them by class, transient and weight (no reference script)")
@@ -487,11 +499,21 @@ def _small_graph(a):
 
 
 def run_census(a):
-    from .census import census, census_minima
+    from .census import census, census_boltzmann, census_marginals, census_minima
+    if a.marginals and a.minima:
+        raise SystemExit("census: --marginals and --minima are separate enumerations; run them one at a time")
+    if not a.marginals and (a.levels is not None or a.lam is not None):
+        raise SystemExit("census: --levels and --lam belong to --marginals")
     t0 = time.time()
     g, edges = _small_graph(a)
     limit = {} if a.max_configs is None else {"max_configs": a.max_configs}
-    res = (census_minima if a.minima else census)(g, a.p, a.c, **limit)
+    if a.marginals:
+        res = census_marginals(g, a.p, a.c, levels=a.levels, **limit)
+        if a.lam is not None:
+            per = [census_boltzmann(res, a.lam, level=i) for i in range(len(res["levels"]))]
+            res.update(lam=np.asarray(a.lam, dtype=np.float64), **{k: np.stack([b[k] for b in per]) for k in per[0]})
+    else:
+        res = (census_minima if a.minima else census)(g, a.p, a.c, **limit)
     res["edges"] = edges
     out = a.out or f"census_{a.graph}.npz"
     np.savez(out, **res)
@@ -502,6 +524,10 @@ def run_census(a):
         print(f"census: minimal consensus sets {res['minima_total'].tolist()}, of them optimal "
               f"{[int(res['minima'][t, k]) for t, k in enumerate(res['min_plus'])]}, max_plus "
               f"{res['max_plus'].tolist()}, mean_plus {np.round(res['mean_plus'], 3).tolist()}", flush=True)
+    if a.marginals:
+        print(f"census: levels {res['levels']}, optimal configurations {res['optimal'].tolist()}, backbone +1 "
+              f"{res['backbone_plus'].sum(axis=1).tolist()} and -1 {res['backbone_minus'].sum(axis=1).tolist()} of "
+              f"{a.n} nodes", flush=True)
     return res
 
 

@@ -485,6 +485,33 @@ __global__ void __launch_bounds__(256) k_bdcm_edge_obs(const double* __restrict_
     edge_obs_item(chi + e * NC, chi + (e + E) * NC, edges, deg, e, T, ab, eps, zij, mterm);
 }
 
+// The two endpoint terms of edge_obs_item's m_init term apart and without the degrees:
+// m_uv[2e] = <s_u(0)>_e and m_uv[2e+1] = <s_v(0)>_e under the edge's own measure f b / Zij, summed in the
+// same order (messages u -> v at row e, v -> u at row e + E)
+__global__ void __launch_bounds__(256) k_bdcm_edge_m(const double* __restrict__ chi, int64_t E, int T, int ab,
+                                                     double eps, double* __restrict__ m_uv) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int X = 1 << T, XV = X / 2, NC = 1 << (2 * T);
+    const double* f = chi + e * NC;
+    const double* b = chi + (e + E) * NC;
+    double z = 0.0, mu = 0.0, mv = 0.0;
+    for (int a = XV - 1; a >= 0; --a) {
+        const int xa = 2 * a + ab;
+        const double sa = (double)bspin(xa, 0, T);
+        for (int c = XV - 1; c >= 0; --c) {
+            const int xb = 2 * c + ab;
+            const double pr = f[xa * X + xb] * b[xb * X + xa];
+            z += pr;
+            mu += sa * pr;
+            mv += (double)bspin(xb, 0, T) * pr;
+        }
+    }
+    z = (z < eps) ? eps : z;
+    m_uv[2 * e] = mu / z;
+    m_uv[2 * e + 1] = mv / z;
+}
+
 // the same with the two rows of every edge given explicitly (a union of graphs:
 // the reverse of a forward row is not "row + E")
 __global__ void __launch_bounds__(256) k_bdcm_edge_obs_batch(const double* __restrict__ chi,
@@ -680,6 +707,17 @@ extern "C" int mjx_bdcm_edge_obs(const double* chi, const int32_t* edges, const 
     k_bdcm_edge_obs<<<(unsigned)((E + 255) / 256), 256, 0, as_stream(stream)>>>(
         chi, edges, deg, E, p + c, attr_value > 0 ? 1 : 0, eps, zij, m_term);
     MJX_LAUNCH_CHECK("k_bdcm_edge_obs");
+    return MJX_OK;
+}
+
+extern "C" int mjx_bdcm_edge_m(const double* chi, int64_t E, int p, int c, int attr_value, double eps, double* m_uv,
+                               void* stream) {
+    if (E < 0 || p < 0 || c < 1 || p + c > kMaxT || (attr_value != 1 && attr_value != -1)) return MJX_EINVAL;
+    if (E == 0) return MJX_OK;
+    if (!chi || !m_uv) return MJX_EINVAL;
+    k_bdcm_edge_m<<<(unsigned)((E + 255) / 256), 256, 0, as_stream(stream)>>>(chi, E, p + c, attr_value > 0 ? 1 : 0,
+                                                                              eps, m_uv);
+    MJX_LAUNCH_CHECK("k_bdcm_edge_m");
     return MJX_OK;
 }
 

@@ -1,7 +1,8 @@
 // Exact enumerations of a small graph (no reference counterpart; definitions
 // in include/mjx.h): every configuration x in [0, 2^n) is run under the
 // always-stay majority rule.  k_census runs T steps and counts, in
-// counts[t][popcount(x)], the x whose onestep^t(x) is all +1; k_census_minima
+// counts[t][popcount(x)], the x whose onestep^t(x) is all +1, and with CnNodeArgs
+// also counts those of one level per +1 node; k_census_minima
 // counts the minimal elements of those levels from their bitmap;
 // k_attractor_census runs every x until s(t+2) = s(t) and counts it by class,
 // transient and weight.
@@ -270,22 +271,85 @@ __device__ __forceinline__ u64 cn_sweep(const CnFrame& F, int n, const u64* __re
 // k_census's own cells: hist[CN_MAXT + 1][n + 1] and the smallest key of every level, u64
 __host__ __device__ inline size_t cn_cells(int64_t n) { return (size_t)(CN_MAXT + 1) * (n + 2) * sizeof(u64); }
 
+// the node cells behind k_census's own when it counts per node: node[n + 1][n], 32 bits each (n (n + 1) is
+// even: a multiple of 8 bytes)
+__host__ __device__ inline size_t cn_node_cells(int64_t n) { return (size_t)(n + 1) * n * sizeof(uint32_t); }
+
+// The configurations m of the lane's block b into node[k][v] for every +1 node v of each, k as in cn_bin.
+// Node v < 6 is a bit of the position in the word: the level-0 pattern picks its configurations.  Node
+// v >= 6 is bit v - 6 of b: set, it takes the whole word.  A row that starts at a multiple of 64 (`first`,
+// wave-uniform) has the bits from 6 on of b the same in every lane, so the words of the wave are summed by
+// weight once -- k = popcount(first >> 6) + j, j = popcount(lane) + the weight in the word = 0..12 -- and
+// lane l adds the 13 sums for node 12 + l; in any other row every lane adds for its own b.  Nothing is
+// touched when m is empty in every lane.
+__device__ __forceinline__ void cn_bin_nodes(uint32_t* node, int n, u64 m, int kb, u64 b, u64 first) {
+    if (__ballot(m != 0) == 0) return;
+    const int lane = threadIdx.x;
+    const bool aligned = (first & 63) == 0;
+    const int own_end = (aligned && n > 12) ? 12 : n;                // below: the nodes a lane adds for itself
+    int cw[7];
+#pragma unroll
+    for (int w = 0; w <= 6; ++w) {
+        const u64 x = m & cn_weight(w);
+        cw[w] = __popcll(x);
+        if (x) {
+            uint32_t* row = node + (kb + w) * n;
+#pragma unroll
+            for (int v = 0; v < 6; ++v) {
+                const int in = __popcll(x & cn_pattern(v));
+                if (v < n && in) atomicAdd(&row[v], (uint32_t)in);
+            }
+            for (int v = 6; v < own_end; ++v)
+                if ((b >> (v - 6)) & 1) atomicAdd(&row[v], (uint32_t)cw[w]);
+        }
+    }
+    if (own_end == n) return;
+    const int pl = __popc(lane), v = 12 + lane;
+    const bool mine = v < n && ((first >> (v < n ? v - 6 : 0)) & 1);
+    uint32_t* col = node + __popcll(first >> 6) * n + (mine ? v : 0);
+#pragma unroll
+    for (int j = 0; j <= 12; ++j) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w <= 6; ++w) s = (j - pl == w) ? cw[w] : s;
+        for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
+        if (mine && s) atomicAdd(&col[j * n], (uint32_t)s);
+    }
+}
+
+// k_census's trailing argument when it also counts per node: the level, and node_counts[n + 1][n]
+struct CnNodeArgs {
+    int t_node;
+    u64* out;
+};
+__device__ __forceinline__ CnNodeArgs cn_node_args() { return {0, nullptr}; }
+__device__ __forceinline__ CnNodeArgs cn_node_args(CnNodeArgs a) { return a; }
+
 // A full block stays full (all +1 is a fixed point), so a row is swept only while some lane's is not.
 // MASK: the level's word of every block of the range is stored at bits[t * B + b], the words of the
-// levels that are not swept (zero words, full blocks) included; without it no mask code is compiled
-template <class Adj, bool MASK>
+// levels that are not swept (zero words, full blocks) included; without it no mask code is compiled.
+// Nodes: nothing, or CnNodeArgs: the configurations of level t_node are also counted per +1 node, in
+// 32-bit cells behind the keys that are added to `out` at the end.  An empty pack leaves the kernel's
+// arguments and code as they are without it.
+template <class Adj, bool MASK, class... Nodes>
 __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo, u64 block_hi,
                                                u64* __restrict__ counts, u64* __restrict__ witness,
-                                               int32_t* __restrict__ flag, u64* __restrict__ bits) {
+                                               int32_t* __restrict__ flag, u64* __restrict__ bits, Nodes... nodes) {
+    constexpr bool NODES = sizeof...(Nodes) > 0;
     const int lane = threadIdx.x;
     const int cells = (T + 1) * (n + 1);
     CnFrame F;
     u64 *hist, *best;
-    if (!cn_frame(A, n, flag, F, cn_cells(n), [&](unsigned char* own) {
+    uint32_t* node;
+    if (!cn_frame(A, n, flag, F, cn_cells(n) + (NODES ? cn_node_cells(n) : 0), [&](unsigned char* own) {
             hist = (u64*)own;
             best = hist + (CN_MAXT + 1) * (n + 1);
             for (int i = lane; i < cells; i += 64) hist[i] = 0;
             if (lane <= CN_MAXT) best[lane] = ~0ull;
+            if (NODES) {
+                node = (uint32_t*)(own + cn_cells(n));
+                for (int i = lane; i < (n + 1) * n; i += 64) node[i] = 0;
+            }
         }))
         return;
 
@@ -307,12 +371,16 @@ __global__ void __launch_bounds__(64) k_census(Adj A, int n, int T, u64 block_lo
             }
             if (MASK && active) bits[(u64)t * B + b] = mask;
             cn_bin<CN_LIGHTEST>(hist + t * (n + 1), mask, kb, b, &best[t]);
+            if (NODES && t == cn_node_args(nodes...).t_node) cn_bin_nodes(node, n, mask, kb, b, first);
         }
     }
     __syncthreads();
     for (int i = lane; i < cells; i += 64)
         if (hist[i]) atomicAdd(&counts[i], hist[i]);
     if (lane <= T && best[lane] != ~0ull) atomicMin(&witness[lane], best[lane]);
+    if (NODES)
+        for (int i = lane; i < (n + 1) * n; i += 64)
+            if (node[i]) atomicAdd(&cn_node_args(nodes...).out[i], (u64)node[i]);
 }
 
 // The minimal elements of a bitmap's levels.  No adjacency and no sweep: a wave owns the 64 consecutive
@@ -537,6 +605,29 @@ static int census_run(int rc, Adj A, int64_t n, int p, int c, int64_t block_lo, 
 }
 
 template <class Adj>
+static int census_nodes_run(int rc, Adj A, int64_t n, int p, int c, int t_node, int64_t block_lo, int64_t block_hi,
+                            int grid, unsigned long long* counts, unsigned long long* witness_key,
+                            unsigned long long* node_counts, int32_t* flag, void* stream) {
+    if (rc) return rc;
+    if (p < 0 || c < 0 || p + c - 1 < 0 || n < 1 || !counts || !witness_key || !node_counts || !flag || grid < 0)
+        return MJX_EINVAL;
+    if (n > CN_MAXN || p + c - 1 > CN_MAXT) return MJX_ERANGE;
+    if (t_node < 0 || t_node > p + c - 1) return MJX_EINVAL;
+    const size_t lds = cn_lds(n).total() + cn_cells(n) + cn_node_cells(n);
+    if (lds > kCnLdsMax) return MJX_EINVAL;
+    if (!cn_range_ok(n, block_lo, block_hi)) return MJX_EINVAL;
+    // a workgroup's 32-bit node cell counts at most the 64 * 2^25 = 2^31 configurations of the launch
+    if (block_hi - block_lo > ACN_MAXBLOCKS) return MJX_ERANGE;
+    if (block_lo == block_hi) return MJX_OK;
+    const int g = cn_grid(lds, block_hi - block_lo, grid);
+    k_census<Adj, false, CnNodeArgs><<<(unsigned)g, 64, lds, as_stream(stream)>>>(
+        A, (int)n, p + c - 1, (u64)block_lo, (u64)block_hi, counts, witness_key, flag, nullptr,
+        CnNodeArgs{t_node, (u64*)node_counts});
+    MJX_LAUNCH_CHECK("k_census<nodes>");
+    return MJX_OK;
+}
+
+template <class Adj>
 static int attractor_census_run(int rc, Adj A, int64_t n, int t_max, int64_t block_lo, int64_t block_hi, int grid,
                                 unsigned long long* hist, unsigned long long* unsettled, unsigned long long* keys,
                                 int32_t* flag, unsigned long long* stats, void* stream) {
@@ -614,6 +705,28 @@ extern "C" int mjx_census_mask_csr(const int64_t* row_ptr, const int32_t* col, i
                                    unsigned long long* witness_key, int32_t* flag, uint64_t* mask, void* stream) {
     return census_run(cn_check_csr(row_ptr), CnCsr{row_ptr, col}, n, p, c, block_lo, block_hi, grid, counts,
                       witness_key, flag, true, mask, stream);
+}
+
+extern "C" int64_t mjx_census_nodes_lds(int64_t n) {
+    if (n < 1 || n > CN_MAXN) return -1;
+    const size_t b = cn_lds(n).total() + cn_cells(n) + cn_node_cells(n);
+    return b > kCnLdsMax ? -1 : (int64_t)b;
+}
+
+extern "C" int mjx_census_nodes_ell(const int32_t* adj, int64_t n, int d, int p, int c, int t_node, int64_t block_lo,
+                                    int64_t block_hi, int grid, unsigned long long* counts,
+                                    unsigned long long* witness_key, unsigned long long* node_counts, int32_t* flag,
+                                    void* stream) {
+    return census_nodes_run(cn_check_ell(adj, d), CnEll{adj, d}, n, p, c, t_node, block_lo, block_hi, grid, counts,
+                            witness_key, node_counts, flag, stream);
+}
+
+extern "C" int mjx_census_nodes_csr(const int64_t* row_ptr, const int32_t* col, int64_t n, int p, int c, int t_node,
+                                    int64_t block_lo, int64_t block_hi, int grid, unsigned long long* counts,
+                                    unsigned long long* witness_key, unsigned long long* node_counts, int32_t* flag,
+                                    void* stream) {
+    return census_nodes_run(cn_check_csr(row_ptr), CnCsr{row_ptr, col}, n, p, c, t_node, block_lo, block_hi, grid,
+                            counts, witness_key, node_counts, flag, stream);
 }
 
 extern "C" int mjx_census_minima(const uint64_t* mask, int64_t n, int T, int64_t block_lo, int64_t block_hi, int grid,
